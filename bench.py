@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- walker-lnprob evals/sec on N MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config C1|C2|C3|C4] [--strong] [--walkers n]
+    python bench.py --gpus N --steps K --warmup W [--config C1|C2|C3|C4] [--strong] [--walkers n] [--dump-outputs DIR] [--full]
 
 Works as typed for any N: with N > 1 and no torchrun environment the script starts N ranks itself
 (``python -m torch.distributed.run`` as a CHILD process, before anything in this process touches
@@ -10,23 +10,29 @@ the GPU) and relays rank 0's JSON line; under torchrun (how the driver starts it
 A "step" is one pass of the hot path over one batch: lnprob of the rank's block of walkers (theta
 already resident in HBM, lnprob left in HBM) and, for N > 1, the blocking RCCL all-gather of the
 per-walker lnprob vector that a single ensemble needs before its next half-step (north_star's
-"RCCL gather of per-walker lnprob"; the *strict* form).  The island form (every rank samples its
-own walkers, gathers shipped asynchronously in chunks) and the gather-free time are reported
-beside it in ``gather``.
+"RCCL gather of per-walker lnprob"; the *strict* form).  With ``--full`` the island form (every
+rank samples its own walkers, gathers shipped asynchronously in chunks) and the gather-free time
+are reported beside it in ``gather``.
 
 Workload: BASELINE.json configs[1] per GPU by default ("C1": MgII 2796/2803, z=0.348, 2
 components, 4096 px, 23-tap Gaussian LSF, 512 walkers per GPU => weak scaling).  ``--config
 C2|C3|C4`` selects the other configs (per-GPU share of their walker count: C2 1024, C3 2048/8,
-C4 4096/8); ``--strong`` fixes the config's TOTAL walker count and splits it W/N.
+C4 4096/8); ``--strong`` fixes the config's TOTAL walker count and splits it W/N.  The inputs are
+seeded: the same arguments give the same theta batch and spectra in every run.
 
 Timing: W untimed warm-up steps (raised to what the GPU needs to reach steady clocks; the number
-actually run is ``warmup_effective``), then ``repeats`` blocks of EXACTLY K steps, each bracketed
-by barrier + synchronize on both sides and max-reduced over ranks; ``ms_per_step`` is the MEDIAN
-block (>= ``--min-seconds`` = 2 s of timed passes in total, so a short ``--steps`` is not a one-shot
-sample and the driver's GPU-busy sampler sees the run).  ``value`` is the device-resident rate (theta
-in HBM when the timed region starts: the bench contract); ``value_host_entry`` is the same batch
-through ``vp_lnprob_batch`` with host buffers (the seam north_star names), timed as long.
-One JSON line on rank 0.
+actually run is ``warmup_effective``), then ONE block of exactly K steps (``--repeats R``: R such
+blocks), bracketed by barrier + synchronize on both sides and max-reduced over ranks;
+``ms_per_step`` is that block's time / K (the median block where there are several).  ``value`` is
+the device-resident rate (theta in HBM when the timed region starts: the bench contract).
+``--dump-outputs DIR`` writes what the last timed step computed (the arrays a caller of the path
+receives) as DIR/<name>.npy.  One JSON line on rank 0.
+
+A plain run measures only that.  ``--full`` adds everything else the benchmark reports: timed
+blocks up to ``--min-seconds`` (2 s) of passes, the roofline leg, ``value_host_entry`` (the same
+batch through ``vp_lnprob_batch`` with host buffers, the seam north_star names), copy bandwidth,
+the device samplers, posterior-spread and side-by-side passes, the multi-rank gather comparisons
+and the CPU baselines (``--no-extras`` / ``--no-cpu-baseline`` switch parts of it off).
 """
 import argparse
 import json
@@ -52,6 +58,48 @@ WORKLOAD_LABEL = {
 }
 # total walkers of the config (BASELINE.json) and the GPU count it is quoted on
 CONFIG_WALKERS = {"C0": (50, 1), "C1": (512, 1), "C2": (1024, 1), "C3": (2048, 8), "C4": (4096, 8)}
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs writes at most this much in all
+
+
+def timed_blocks(args, t_step):
+    """Timed blocks of exactly --steps passes: --repeats if given, else one -- or, with --full, as many as --min-seconds of passes
+    need (>= 3: the driver's GPU-busy sampler and its own clock can then corroborate the line)."""
+    if args.repeats > 0:
+        return args.repeats
+    if not args.full:
+        return 1
+    return int(min(50000, max(3, np.ceil(args.min_seconds / max(args.steps * t_step, 1e-9)))))
+
+
+def _take(a, idx):
+    """a[idx] along the first axis, for a numpy array or a torch tensor (indexed where it lives)."""
+    if hasattr(a, "cpu"):
+        import torch
+        return a[torch.as_tensor(idx, device=a.device)]
+    return a[idx]
+
+
+def write_outputs(out_dir, arrays, limit_bytes=DUMP_LIMIT_BYTES):
+    """--dump-outputs: each array (numpy or torch) as out_dir/<name>.npy in float64.  Where together they hold more than
+    limit_bytes, each keeps a fixed, seeded sample within its share of the limit (the same sorted indices for the same shapes in
+    every run), so that two builds can be compared output for output: whole rows where a row fits in that share, else elements of
+    the flattened array.  The files never hold more than limit_bytes of data in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(8 * int(np.prod(a.shape)) for a in arrays.values())
+    for name, a in arrays.items():
+        if total > limit_bytes:
+            size = 8 * int(np.prod(a.shape))
+            budget = limit_bytes * size // total               # < size, since total > limit_bytes
+            n = int(a.shape[0]) if len(a.shape) else 0
+            if n > 0 and 0 < size // n <= budget:
+                keep = budget // (size // n)
+            else:
+                a, n = a.reshape(-1), size // 8
+                keep = budget // 8
+            a = _take(a, np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False)))
+        if hasattr(a, "cpu"):
+            a = a.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def parse_args(argv=None):
@@ -63,7 +111,8 @@ def parse_args(argv=None):
     ap.add_argument("--walkers", type=int, default=None, help="walkers per GPU (default: the config's per-GPU share)")
     ap.add_argument("--strong", action="store_true",
                     help="strong scaling: the config's TOTAL walker count (or --walkers x 1) split over the GPUs")
-    ap.add_argument("--repeats", type=int, default=0, help="timed blocks of --steps passes (0 = enough for 0.25 s)")
+    ap.add_argument("--repeats", type=int, default=0,
+                    help="timed blocks of --steps passes (0 = one block; with --full, as many as --min-seconds needs)")
     ap.add_argument("--spread", default="ball", choices=["ball", "posterior"],
                     help="walker positions of the timed passes: 'ball' = SURVEY 8(d)'s 1e-3 ball around theta_true (the default, what "
                          "`value` is defined on), 'posterior' = the ensemble after a burn-in of the device-resident stretch sampler")
@@ -71,7 +120,14 @@ def parse_args(argv=None):
                     help="which C-ABI entry a step is: 'lnprob' (vp_lnprob_batch_device: the headline) or 'model_flux' "
                          "(vp_model_flux_batch_device, the (W, P) convolved model flux: seam 3 of SURVEY 8b, HBM-write-bound)")
     ap.add_argument("--min-seconds", type=float, default=2.0,
-                    help="lower bound on the TOTAL timed region (sum of the timed blocks), so that an outside observer sees the GPU busy")
+                    help="with --full: lower bound on the TOTAL timed region (sum of the timed blocks), so that an outside observer "
+                         "sees the GPU busy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what is not the headline figure (see the module docstring); off: set up, warm up, "
+                         "time the steps, write --dump-outputs, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64; a fixed, seeded sample of "
+                         "rows where the arrays exceed 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the legs that are not part of `value` (copy bandwidth, host-entry latency, device sampler): "
@@ -301,11 +357,35 @@ def model_flux_main(args, wl, d_theta, stream, rank, world, use_dist, spread_not
     warm_eff = max(args.warmup, int(min(1500, max(20, 0.05 / max(t_probe, 1e-6)))))
     for _ in range(warm_eff):
         step()
-    repeats = args.repeats if args.repeats > 0 else int(min(50000, max(3, np.ceil(args.min_seconds / max(args.steps * t_probe, 1e-9)))))
+    repeats = timed_blocks(args, t_probe)
     ts = [timed(args.steps) for _ in range(repeats)]
     elapsed = float(np.median(ts))
     if rank != 0:
         return 0
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, {"model_flux_%d" % k: b for k, b in enumerate(bufs)})
+    line = {
+        "metric": "model_flux walker-evals/sec", "value": W * world * args.steps / elapsed, "unit": "evals/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "warmup_effective": warm_eff, "repeats": repeats,
+        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "strong" if args.strong else "weak",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": WORKLOAD_LABEL[args.config] + " -- entry model_flux (vp_model_flux_batch_device, convolved)",
+                   "walkers_per_gpu": W, "walkers_total": W * world, "ndim": D, "n_lines": wl.n_lines, "pixels": wl.pixels,
+                   "parallelism": f"walker-shard x{world}"},
+        "walker_spread": spread_note,
+    }
+    if args.full:
+        model_flux_full(args, wl, step, stream, line)
+    print(json.dumps(line), flush=True)
+    return 0
+
+
+def model_flux_full(args, wl, step, stream, line):
+    """--full legs of --entry model_flux: kernel-side timing with and without the far-field expansions, roofline, copy bandwidth,
+    the host-buffer entry and (one rank) the CPU baseline with its parity check, added to `line`."""
+    import torch
+    eng = wl.engine
+    W, D = wl.thetas.shape
     # live kernel-side timing: HIP events on the launch stream around back-to-back steps, with and without the far-field
     # expansions serving the flux path
     def ev_ms(n=100):
@@ -359,20 +439,12 @@ def model_flux_main(args, wl, d_theta, stream, rank, world, use_dist, spread_not
         for k in range(len(wl.pixels)):
             got = wl.engine.model_flux(k, wl.thetas)
     host_s = (time.perf_counter() - th0) / nh
-    line = {
-        "metric": "model_flux walker-evals/sec", "value": W * world * args.steps / elapsed, "unit": "evals/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "warmup_effective": warm_eff, "repeats": repeats,
-        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "strong" if args.strong else "weak",
-        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": WORKLOAD_LABEL[args.config] + " -- entry model_flux (vp_model_flux_batch_device, convolved)",
-                   "walkers_per_gpu": W, "walkers_total": W * world, "ndim": D, "n_lines": wl.n_lines, "pixels": wl.pixels,
-                   "parallelism": f"walker-shard x{world}"},
-        "walker_spread": spread_note,
+    line.update({
         "value_host_entry": W / host_s, "host_entry_ms_per_call": 1e3 * host_s,
         "host_entry_note": "vp_model_flux_batch: theta H2D + kernels + (W, P) rows D2H over PCIe (%.1f MB per call)" % (bytes_written / 1e6),
         "roofline": roof,
-    }
-    if world == 1 and not args.no_cpu_baseline:
+    })
+    if line["n_gpus"] == 1 and not args.no_cpu_baseline:
         from oracle import voigt_oracle as vo           # checker / baseline only, never the product
         insts = _oracle_instruments(vo, _describe(wl))
         n, t0 = 0, time.perf_counter()
@@ -390,15 +462,13 @@ def model_flux_main(args, wl, d_theta, stream, rank, world, use_dist, spread_not
         line["cpu_baseline"] = dict(value=n / dt, unit="model_flux walker-evals/s", cores=1, kind="port",
                                     sample=f"{n} serial model_flux calls over the {wl.name} walker rows ({dt:.1f} s, numpy/scipy oracle)")
         line["parity_vs_cpu_baseline_max_abs_flux"] = worst
-    print(json.dumps(line), flush=True)
-    return 0
 
 
 def rank_main(args):
     # The CPU fan-out leg forks its workers BEFORE anything touches the GPU (a context is not
     # fork-safe and forked children must not hold the device); they idle until the bench is done.
     pool, pool_cores = None, 0
-    if (int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu_baseline
+    if (args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu_baseline
             and not any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ)):
         import multiprocessing as mp
         pool_cores = host_cores()                      # all host cores the box reports for this process
@@ -539,15 +609,18 @@ def rank_main(args):
     warm_eff = max(args.warmup, int(min(1500, max(20, 0.05 / max(t_probe, 1e-6)))))
     for _ in range(warm_eff):
         strict_step()
-    # timed region: blocks of exactly --steps passes, as many as --min-seconds of passes need (>= 2 s by default: the driver's
-    # GPU-busy sampler and its own clock can then corroborate the line)
-    repeats = args.repeats if args.repeats > 0 else int(min(50000, max(3, np.ceil(args.min_seconds / max(args.steps * t_probe, 1e-9)))))
+    # timed region: blocks of exactly --steps passes (one in a plain run)
+    repeats = timed_blocks(args, t_probe)
     elapsed, block_times = blocks(strict_step, args.steps, repeats, drain=strict_drain)
-    rccl_ms = None
     if direct is not None:
         torch.cuda.synchronize()
         if direct.timed_out():
             raise SystemExit("bench.py: a device-side wait of the direct gather timed out")
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives after its last step: the whole gathered vector where there are ranks
+        write_outputs(args.dump_outputs, {"lnprob": direct.gathered if direct is not None else (gathered if use_dist else d_out)})
+    rccl_ms = None
+    if direct is not None and args.full:
         launch(d_out)
         torch.cuda.synchronize()
         me = direct.gathered[rank * W:(rank + 1) * W]
@@ -558,9 +631,9 @@ def rank_main(args):
     # chunk of steps runs on RCCL's stream, double-buffered, under the next chunk's kernels; and the gather-free
     # form -- neither is `value`
     island_ms = nogather_ms = None
-    if use_dist:
+    gather_every = int(os.environ.get("BENCH_GATHER_EVERY", "128"))
+    if use_dist and args.full:
         from rbvfit_amd.dist import PipelinedGather
-        gather_every = int(os.environ.get("BENCH_GATHER_EVERY", "128"))
         pg = PipelinedGather(launch, W, device="cuda", every=gather_every)
         for _ in range(min(warm_eff, 2 * gather_every)):
             pg.step()
@@ -572,7 +645,7 @@ def rank_main(args):
 
     # ---- roofline leg: HIP events around the tile kernel on its launch stream (rank 0) -------
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         eng.profile_enable(True)
         nprof = min(max(args.steps, 20), 200)
         for _ in range(nprof):
@@ -822,7 +895,7 @@ def rank_main(args):
                 multi_info = {"error": str(e)}
 
     side_info = None
-    if rank == 0 and not args.no_extras and args.config in ("C0", "C1"):
+    if rank == 0 and args.full and not args.no_extras and args.config in ("C0", "C1"):
         # Two independent ensembles (two contexts, two streams) evaluated side by side: what one GPU sustains for a caller with more
         # than one chain in flight (tempered chains, several absorbers fitted at once).  A lone stream of dependent passes leaves
         # the SIMDs idle through every launch's entry; a second stream's passes move into those gaps.  Not `value`.
@@ -861,7 +934,6 @@ def rank_main(args):
         except Exception as e:                                   # (an extra: never fails the line)
             side_info = {"error": str(e)}
 
-    result = d_out.cpu().numpy()
     if rank == 0:
         evals = W * world * args.steps
         line = {
@@ -878,31 +950,34 @@ def rank_main(args):
                        "parallelism": f"walker-shard x{world}" + ((" + direct-write gather per pass" if direct is not None else
                                                                    " + blocking RCCL all_gather per pass") if world > 1 else "")},
             "passes_per_sec": args.steps / elapsed,
-            "mcmc_steps_per_sec": sampler_steps,
-            "mcmc_steps_per_sec_note": "device-resident stretch move (vp_stretch_run): one ensemble step = two half-ensemble "
-                                       "launches (proposal, lnprob, accept / reject inside each walker's workgroup; consecutive half-steps "
-                                       "overlap on two streams, every walker waiting for its partner's row only); rank 0's walkers; wall "
-                                       "time around the call, upload of the start positions and download of the final state included",
-            "slice_sampler": slice_info,
-            "slice_sampler_note": "device-resident ensemble slice sampling (vp_slice_run, zeus' differential move): ensemble steps/s, "
-                                  "lnprob evaluations per walker and step, and the evaluations/s they amount to",
-            "value_host_entry": host_rate,
-            "value_definition": "`value`: theta resident in HBM when the timed region starts and lnprob left in HBM (vp_lnprob_batch_device; the "
-                                "bench contract's definition, PCIe-inclusive rates are never `value`).  `value_host_entry`: the same batch through "
-                                "vp_lnprob_batch with host buffers -- what north_star's sampler loop and SURVEY 8(d)'s 'wall time around "
-                                "vp_lnprob_batch including H2D/D2H' describe (emcee vectorize=True, the INTEGRATION.md stub) --, timed over as "
-                                "many seconds, calls back to back as a sampler makes them (so the library's pre-armed launch of the next call "
-                                "is in play: host_entry_latency.prearm has the same loop without it and a caller with 100 us between calls); "
-                                "both are first-class numbers of this line",
-            "seam_evals_per_sec": host_rate,
-            "host_entry_evals_per_sec_pcie_inclusive": host_rate,
-            "host_entry_latency": host_lat,
             "walker_spread": spread_note,
-            "posterior_spread": spread_info if not args.no_extras else None,
-            "sharded_sampler_one_gpu": multi_info if not args.no_extras else None,
-            "two_ensembles_side_by_side": side_info,
-            "roofline": roof,
         }
+        if args.full:
+            line.update({
+                "mcmc_steps_per_sec": sampler_steps,
+                "mcmc_steps_per_sec_note": "device-resident stretch move (vp_stretch_run): one ensemble step = two half-ensemble "
+                                           "launches (proposal, lnprob, accept / reject inside each walker's workgroup; consecutive half-steps "
+                                           "overlap on two streams, every walker waiting for its partner's row only); rank 0's walkers; wall "
+                                           "time around the call, upload of the start positions and download of the final state included",
+                "slice_sampler": slice_info,
+                "slice_sampler_note": "device-resident ensemble slice sampling (vp_slice_run, zeus' differential move): ensemble steps/s, "
+                                      "lnprob evaluations per walker and step, and the evaluations/s they amount to",
+                "value_host_entry": host_rate,
+                "value_definition": "`value`: theta resident in HBM when the timed region starts and lnprob left in HBM (vp_lnprob_batch_device; the "
+                                    "bench contract's definition, PCIe-inclusive rates are never `value`).  `value_host_entry`: the same batch through "
+                                    "vp_lnprob_batch with host buffers -- what north_star's sampler loop and SURVEY 8(d)'s 'wall time around "
+                                    "vp_lnprob_batch including H2D/D2H' describe (emcee vectorize=True, the INTEGRATION.md stub) --, timed over as "
+                                    "many seconds, calls back to back as a sampler makes them (so the library's pre-armed launch of the next call "
+                                    "is in play: host_entry_latency.prearm has the same loop without it and a caller with 100 us between calls); "
+                                    "both are first-class numbers of this line",
+                "seam_evals_per_sec": host_rate,
+                "host_entry_evals_per_sec_pcie_inclusive": host_rate,
+                "host_entry_latency": host_lat,
+                "posterior_spread": spread_info if not args.no_extras else None,
+                "sharded_sampler_one_gpu": multi_info if not args.no_extras else None,
+                "two_ensembles_side_by_side": side_info,
+                "roofline": roof,
+            })
         if use_dist:
             line["gather"] = {"value_form": ("strict: every pass's lnprob block written by the launch itself into every rank's gathered "
                                              "vector (peer-mapped stores, one flag per rank; the next pass waits for it on the device): "
@@ -911,16 +986,19 @@ def rank_main(args):
                               "direct_gather": direct is not None, "direct_gather_unavailable_because": direct_reason or None,
                               "direct_gather_probe": direct_reason or "clean: two passes matched all_gather_into_tensor on every rank",
                               "ranks_seen_by_rccl": dist.get_world_size(), "backend": dist.get_backend(),
-                              "visible_gpus_on_rank0": torch.cuda.device_count(),
-                              "ms_per_step_blocking_rccl_all_gather": rccl_ms if rccl_ms is not None else line["ms_per_step"],
-                              "ms_per_step_island_form": island_ms,
-                              "island_form": f"async all_gather_into_tensor of {gather_every}-step chunks, double-buffered, "
-                                             "overlapped with the following passes (rbvfit_amd.dist.PipelinedGather)",
-                              "island_form_evals_per_sec": W * world / (island_ms * 1e-3),
-                              "ms_per_step_without_gather": nogather_ms,
-                              "blocking_gather_cost_us": 1e3 * (line["ms_per_step"] - nogather_ms),
-                              "overlapped_gather_cost_us": 1e3 * (island_ms - nogather_ms)}
-        if world == 1 and not args.no_cpu_baseline:
+                              "visible_gpus_on_rank0": torch.cuda.device_count()}
+        if use_dist and args.full:
+            line["gather"].update({
+                "ms_per_step_blocking_rccl_all_gather": rccl_ms if rccl_ms is not None else line["ms_per_step"],
+                "ms_per_step_island_form": island_ms,
+                "island_form": f"async all_gather_into_tensor of {gather_every}-step chunks, double-buffered, "
+                               "overlapped with the following passes (rbvfit_amd.dist.PipelinedGather)",
+                "island_form_evals_per_sec": W * world / (island_ms * 1e-3),
+                "ms_per_step_without_gather": nogather_ms,
+                "blocking_gather_cost_us": 1e3 * (line["ms_per_step"] - nogather_ms),
+                "overlapped_gather_cost_us": 1e3 * (island_ms - nogather_ms)})
+        if world == 1 and args.full and not args.no_cpu_baseline:
+            result = d_out.cpu().numpy()
             cb, cpu_vals = cpu_baseline(wl)
             n = min(len(cpu_vals), W)
             if pool is not None:
@@ -935,7 +1013,7 @@ def rank_main(args):
         pool.terminate()
         pool.join()
     if use_dist:
-        if rank == 0 and gathered is not None:
+        if rank == 0 and gathered is not None and args.full:
             assert torch.equal(gathered[:W], d_out), "all-gathered lnprob differs from the local block"
         dist.barrier()                       # rank 0's extra legs are done: leave together
         dist.destroy_process_group()

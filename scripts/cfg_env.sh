@@ -12,7 +12,7 @@ for spec in "$@"; do
     extra=""
     [ "$cfg" = "C3" ] && extra="--walkers ${C3W:-2048}"
     [ "$cfg" = "C4" ] && extra="--walkers ${C4W:-512}"
-    env "${envs[@]}" python bench.py --no-cpu-baseline --no-extras --config $cfg $extra --steps ${STEPS:-40} --warmup 5 2>>$OUT.err | python -c "
+    env "${envs[@]}" python bench.py --full --no-cpu-baseline --no-extras --config $cfg $extra --steps ${STEPS:-40} --warmup 5 2>>$OUT.err | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('[$spec]', '$cfg', d['config']['walkers_per_gpu'], round(d['value']), 'us/step', round(1e3*d['ms_per_step'],1), 'tile_us', round(1e3*r['avg_kernel_ms'],1), 'frac', round(r['frac'],4))" >> $OUT

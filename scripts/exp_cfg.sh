@@ -8,7 +8,7 @@ for spec in "$@"; do
     extra=""
     [ "$cfg" = "C3" ] && extra="--walkers ${C3W:-2048}"
     [ "$cfg" = "C4" ] && extra="--walkers ${C4W:-512}"
-    env RBVFIT_AMD_LIB=$lib python bench.py --no-cpu-baseline --no-extras --config $cfg $extra --steps ${STEPS:-30} --warmup 5 2>>$OUT.err | python -c "
+    env RBVFIT_AMD_LIB=$lib python bench.py --full --no-cpu-baseline --no-extras --config $cfg $extra --steps ${STEPS:-30} --warmup 5 2>>$OUT.err | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('$label', '$cfg', d['config']['walkers_per_gpu'], round(d['value']), 'ms/step', round(d['ms_per_step'],4), 'tile_ms', round(r['avg_kernel_ms'],4), 'prep_ms', round(r['prep_ms'],4), 'frac', round(r['frac'],4))" >> $OUT

@@ -8,7 +8,7 @@ run() {
   envs=()
   while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
   for w in "$@"; do
-    env "${envs[@]}" python bench.py --no-cpu-baseline --no-extras --walkers $w --steps 400 2>>gpurun_out/exp_walker.err | python -c "
+    env "${envs[@]}" python bench.py --full --no-cpu-baseline --no-extras --walkers $w --steps 400 2>>$OUT.err | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('$label', d['config']['walkers_per_gpu'], round(d['value']), round(1e3*d['ms_per_step'],2), round(1e3*r['avg_kernel_ms'],2), round(1e3*r['prep_ms'],2), round(1e3*r['finalize_ms'],2))" >> $OUT

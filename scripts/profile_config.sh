@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box: rocprofv3 kernel-trace stats + separate PMC passes (FETCH_SIZE, WRITE_SIZE, SQ sets) of
-#   python3 bench.py --config <CFG> --no-cpu-baseline --no-extras --steps <S> --warmup 5 [extra bench args]
+#   python3 bench.py --full --config <CFG> --no-cpu-baseline --no-extras --steps <S> --warmup 5 [extra bench args]
 # Usage: scripts/profile_config.sh <tag> <CFG> <steps> [bench args...]   -> gpurun_out/prof_<tag>/{summary.txt,pmc.json,kernel_stats.csv,bench.json}
 set -e
 TAG=$1; CFG=$2; STEPS=$3; shift 3
@@ -8,7 +8,7 @@ REPO=$(pwd)
 OUT=$REPO/gpurun_out/prof_$TAG
 rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
-ARGS="--config $CFG --no-cpu-baseline --no-extras --steps $STEPS --warmup 5 --repeats 3 $@"
+ARGS="--full --config $CFG --no-cpu-baseline --no-extras --steps $STEPS --warmup 5 --repeats 3 $@"
 echo "python3 bench.py $ARGS" > $OUT/command.txt
 python3 bench.py $ARGS > $OUT/bench.json 2> $OUT/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py $ARGS > $OUT/bench_trace.json 2> $OUT/trace.err

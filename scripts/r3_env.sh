@@ -9,7 +9,7 @@ for round in 1 2; do
 for spec in "$@"; do
   [ "$spec" = "-" ] && envs=() || read -r -a envs <<< "$spec"
   for w in ${WS:-256 512}; do
-    env "${envs[@]}" python bench.py --no-cpu-baseline --no-extras --walkers $w --steps 400 2>>$OUT.err | python -c "
+    env "${envs[@]}" python bench.py --full --no-cpu-baseline --no-extras --walkers $w --steps 400 2>>$OUT.err | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('[$spec]', d['config']['walkers_per_gpu'], round(d['value']), 'us/step', round(1e3*d['ms_per_step'],2))" >> $OUT

@@ -6,7 +6,7 @@ O=gpurun_out/$TAG; mkdir -p $O
 : > $O/ab.txt
 line() {   # label lib config-args...
   label=$1; lib=$2; shift 2
-  env RBVFIT_AMD_LIB=$lib python bench.py --no-cpu-baseline --no-extras --min-seconds ${MINS:-0.4} --steps ${STEPS:-200} "$@" 2>>$O/err.txt | python -c "
+  env RBVFIT_AMD_LIB=$lib python bench.py --full --no-cpu-baseline --no-extras --min-seconds ${MINS:-0.4} --steps ${STEPS:-200} "$@" 2>>$O/err.txt | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('$label', d['config']['workload'][:2], d['config']['walkers_per_gpu'], round(d['value']), 'us/step', round(1e3*d['ms_per_step'],2), 'kernel', round(1e3*r['avg_kernel_ms'],2), 'prep', round(1e3*r['prep_ms'],2), 'fin', round(1e3*r['finalize_ms'],2))" >> $O/ab.txt

@@ -6,7 +6,7 @@ for round in 1 2; do
   for spec in "$@"; do
     label=${spec%%:*}; envs=${spec#*:}
     for w in ${WS-256 512}; do
-      env $envs python bench.py --no-cpu-baseline --no-extras --min-seconds ${MINS:-0.4} --steps 200 --walkers $w ${BARGS:-} 2>>$O/err.txt | python -c "
+      env $envs python bench.py --full --no-cpu-baseline --no-extras --min-seconds ${MINS:-0.4} --steps 200 --walkers $w ${BARGS:-} 2>>$O/err.txt | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('$label', d['config']['workload'][:2], d['config']['walkers_per_gpu'], round(d['value']), 'us/step', round(1e3*d['ms_per_step'],2))" >> $O/ab.txt

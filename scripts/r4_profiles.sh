@@ -13,7 +13,7 @@ if [ "$STAGE" = "1" ]; then
   export TMPDIR=/tmp
   for cfg in C1 C2; do
     O=$PWD/gpurun_out/prof_mf_$cfg; rm -rf $O; mkdir -p $O
-    rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --entry model_flux --config $cfg --no-cpu-baseline --steps 100 --warmup 5 --repeats 3 > $O/bench_trace.json 2> $O/trace.err
+    rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --full --entry model_flux --config $cfg --no-cpu-baseline --steps 100 --warmup 5 --repeats 3 > $O/bench_trace.json 2> $O/trace.err
     f=$(find $O/trace -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/kernel_stats.csv; rm -rf $O/trace
     head -6 $O/kernel_stats.csv | cut -c1-160
   done
@@ -22,17 +22,17 @@ else
   for spec in "C1" "C2" "C3 --walkers 2048" "C4 --walkers 512"; do
     read -r -a a <<< "$spec"; cfg=${a[0]}
     st=400; [ "$cfg" = "C2" ] && st=60; [ "$cfg" = "C3" ] && st=40; [ "$cfg" = "C4" ] && st=30
-    python3 bench.py --config "${a[@]}" --no-cpu-baseline --no-extras --steps $st --warmup 5 > $O/${cfg}_bench.json 2> $O/${cfg}_bench.err
+    python3 bench.py --full --config "${a[@]}" --no-cpu-baseline --no-extras --steps $st --warmup 5 > $O/${cfg}_bench.json 2> $O/${cfg}_bench.err
     python3 bench.py --config $cfg --gpus 1 --steps 20 --warmup 5 > $O/${cfg}_bench_driverform.json 2> $O/${cfg}_bench_driverform.err
     python3 - <<PY
 import json
 for f in ("$O/${cfg}_bench.json", "$O/${cfg}_bench_driverform.json"):
-    d = json.loads(open(f).read().strip().splitlines()[-1]); r = d["roofline"]
-    print("$cfg", d["config"]["walkers_per_gpu"], round(d["value"]), "us/step", round(1e3 * d["ms_per_step"], 2), "kernel us", round(1e3 * r["avg_kernel_ms"], 2), "frac", round(r["frac"], 4), "valu_issue", round(r["valu_issue"]["frac"], 3) if r.get("valu_issue") else None, "host_entry", d.get("value_host_entry"), "stretch", d.get("mcmc_steps_per_sec"), "slice", (d.get("slice_sampler") or {}).get("steps_per_sec"))
+    d = json.loads(open(f).read().strip().splitlines()[-1]); r = d.get("roofline") or {}     # (none in the driver's plain line)
+    print("$cfg", d["config"]["walkers_per_gpu"], round(d["value"]), "us/step", round(1e3 * d["ms_per_step"], 2), "kernel us", round(1e3 * r["avg_kernel_ms"], 2) if r else None, "frac", round(r["frac"], 4) if r else None, "valu_issue", round(r["valu_issue"]["frac"], 3) if r.get("valu_issue") else None, "host_entry", d.get("value_host_entry"), "stretch", d.get("mcmc_steps_per_sec"), "slice", (d.get("slice_sampler") or {}).get("steps_per_sec"))
 PY
   done
   for cfg in C1 C2; do
-    python3 bench.py --entry model_flux --config $cfg --steps 20 --warmup 5 > $O/model_flux_$cfg.json 2> $O/model_flux_$cfg.err
+    python3 bench.py --full --entry model_flux --config $cfg --steps 20 --warmup 5 > $O/model_flux_$cfg.json 2> $O/model_flux_$cfg.err
     python3 -c "
 import json; d=json.loads(open('$O/model_flux_$cfg.json').read().strip().splitlines()[-1]); r=d['roofline']
 print('model_flux $cfg', round(d['value']), 'us/step', round(1e3*d['ms_per_step'],2), 'frac', round(r['frac'],4), r['ms_per_step_by_flux_farfield'], 'host', round(d['value_host_entry']), 'cpu', round(d['cpu_baseline']['value']))"

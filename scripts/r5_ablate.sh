@@ -24,8 +24,8 @@ for v in ${ONLY:-$VARIANTS}; do
   n=${v%%:*}
   lib=$PWD/rbvfit_amd/lib/exp/abl_$n.so
   [ -f $lib ] || continue
-  RBVFIT_AMD_LIB=$lib python3 bench.py --no-cpu-baseline --no-extras --min-seconds 0.4 --steps 200 "$@" > $O/$n.json 2> $O/$n.err
-  RBVFIT_AMD_LIB=$lib rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_WAVES --kernel-trace --output-format csv -d $O/pmc_$n -- python3 bench.py --no-cpu-baseline --no-extras --steps 100 --warmup 5 --repeats 2 "$@" > /dev/null 2> $O/pmc_$n.err
+  RBVFIT_AMD_LIB=$lib python3 bench.py --full --no-cpu-baseline --no-extras --min-seconds 0.4 --steps 200 "$@" > $O/$n.json 2> $O/$n.err
+  RBVFIT_AMD_LIB=$lib rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_WAVES --kernel-trace --output-format csv -d $O/pmc_$n -- python3 bench.py --full --no-cpu-baseline --no-extras --steps 100 --warmup 5 --repeats 2 "$@" > /dev/null 2> $O/pmc_$n.err
   python3 - "$O" "$n" >> $O/table.txt <<'PY'
 import sys, json, glob, csv, collections
 O, n = sys.argv[1], sys.argv[2]

@@ -3,7 +3,7 @@
 TAG=$1; CTR=$2; shift 2
 O=$PWD/gpurun_out/pmc_$TAG; rm -rf $O; mkdir -p $O
 export TMPDIR=/tmp
-rocprofv3 --pmc $CTR --kernel-trace --output-format csv -d $O/raw -- python3 bench.py --no-cpu-baseline --no-extras --steps 100 --warmup 5 --repeats 2 "$@" > /dev/null 2> $O/err.txt
+rocprofv3 --pmc $CTR --kernel-trace --output-format csv -d $O/raw -- python3 bench.py --full --no-cpu-baseline --no-extras --steps 100 --warmup 5 --repeats 2 "$@" > /dev/null 2> $O/err.txt
 python3 - "$O" <<'PY'
 import sys, glob, csv, collections
 O = sys.argv[1]

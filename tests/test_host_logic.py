@@ -160,10 +160,9 @@ def test_unknown_wavelength_raises_instead_of_snapping_to_an_unrelated_line(tmp_
         importlib.reload(atomic)
 
 
-REF_ATOMS = "/root/reference/src/rbvfit/lines/atom_full.dat"
+REF_ATOMS = os.path.join(GOLDEN, "atom_full.dat")          # rbvfit's lines/atom_full.dat (320 rows), stored as a fixture
 
 
-@pytest.mark.skipif(not os.path.exists(REF_ATOMS), reason="the reference checkout is only present in the build container")
 def test_builtin_rows_equal_the_reference_list_and_the_full_list_loads():
     import importlib
     at = importlib.reload(atomic)
