@@ -850,7 +850,7 @@ __global__ __launch_bounds__(64 * FF_WAVES) void farfield_kernel2(InstDev I0, In
 // ---------------------------------------------------------------------------------------------
 constexpr int TILE_THREADS_MAX = 256;   // tile_kernel: 1, 2 or 4 waves per workgroup
 constexpr int WALKER_THREADS_MAX = 1024; // walker_kernel: one wave per tile, up to 16 tiles per walker
-constexpr int FL_PAD = 10;        // LDS doubles after a tile's flux that the zero-padded taps may read
+constexpr int FL_PAD = 12;        // zeroed LDS doubles after a tile's flux: every word the zero-padded taps may read (lsf_block6)
 // Diagnostic build (-DVP_STAMPS, scripts/walker_timeline.py): every wave of walker_kernel leaves the shader clock at its
 // phase boundaries in g_stamps[walker][wave][stage]; read back with vp_debug_read_stamps.  Not compiled otherwise.
 // Stages: 0 entry, 1 records ready (behind the first barrier), 2 end of phase A, 3 end of phase B, 4 end of LSF + chi^2,
@@ -1114,6 +1114,10 @@ __device__ __forceinline__ TilePre tile_preload(const InstDev& I, int p0, int no
 // 48 B keeps the 16-byte reads conflict-free (8 lanes x 16 B cover the 32 banks once).  Per output the taps are
 // accumulated in ascending order, as in the plain loop.
 constexpr int LSF_PX = 6;
+// The last word a tap feeding m[] reads is fl[oc + kn + LSF_PX - 2]; oc <= nout - 1 and kn <= K + 7 put it at n_eval + 7 + LSF_PX - 2
+// (K = 1 mod 8, nout = 1 mod LSF_PX).  Words past the zeroed pad are another walker's partial sums (full tiles: red[]) or stale LDS
+// (last tiles), and 0 x NaN poisons chi^2 through the weight-zero outputs below.  FL_PAD even: the Dawson table stays 16-B aligned.
+static_assert(FL_PAD >= 7 + LSF_PX - 1 && FL_PAD % 2 == 0, "FL_PAD must cover the zero taps of the last tap group");
 constexpr int OBS_PAD = 8;         // zeroed doubles behind InstDev::flux / w (capi: vp_add_instrument)
 typedef double obs2_t __attribute__((ext_vector_type(2)));
 typedef obs2_t obs2_u_t __attribute__((aligned(8)));                              // (8-byte aligned: any even OR odd pixel)
@@ -1170,8 +1174,9 @@ __device__ __forceinline__ void lsf_block6(const InstDev& I, const double* __res
     if (OUT == 0 && !EARLY) load_obs();
     if (OUT == 0 && !NANFIX) {
         // outputs of this lane that do not exist (the tile's last lanes) enter with weight zero -- their model values are finite
-        // wherever the tile's own are (the window's tail is the zero padding), their observed pixels the next tile's or the arrays'
-        // padding: a compare and two selects per pixel instead of the masked accumulate's six instructions
+        // only because every flux word their taps reach is either the tile's own or the FL_PAD zeros behind it (see FL_PAD);
+        // their observed pixels are the next tile's or the arrays' padding: a compare and two selects per pixel instead of the
+        // masked accumulate's six instructions
         const int nv = nout - o0;
 #pragma unroll
         for (int p = 0; p < LSF_PX; ++p) {
@@ -1252,7 +1257,7 @@ __device__ __forceinline__ double tile_work(const InstDev& I, rec_t lcw, double*
     const int nwords = (I.L + 63) >> 6;                // 64 lines per mask word
     const int nchunks = (n_eval + 63) >> 6;
     if (first && tid < EXP_LDS_DOUBLES) etab[tid] = PRE ? pre.e2 : exp2_eighth(tid);
-    if (tid < FL_PAD) fl[n_eval + tid] = 0.0;   // what the zero taps multiply must be finite
+    if (tid < FL_PAD) fl[n_eval + tid] = 0.0;   // what the zero taps multiply must be finite (FL_PAD <= 64: one wave writes them)
     // Multi-wave tiles: the exp table is staged by the first wave and read by ALL waves at the end of their first pass.
     // A pass used to be long enough for that never to matter; with the far-field expansions a pass over a block
     // without near lines is ~60 instructions, and a wave could read the table before it was there (C3's 4-wave
@@ -1536,8 +1541,8 @@ __device__ __forceinline__ double tile_work(const InstDev& I, rec_t lcw, double*
     //      (lane stride 16 B: conflict-free) for 16 FMAs -- 5 B of LDS traffic per output and tap
     //      instead of 8 B with one output per lane.  Taps come by scalar loads (SGPR operands of the
     //      FMAs; as LDS broadcasts they were 29 % of the phase's LDS cycles: C3 with its 101 taps +12 %,
-    //      C1 +1.5-2 %), zero-padded to groups of 8; the flux is followed by FL_PAD zeros (the window
-    //      reads at most 9 doubles past the last one).  Per output the taps are still accumulated in ascending order, so the result is
+    //      C1 +1.5-2 %), zero-padded to groups of 8; the flux is followed by FL_PAD zeros (the zero taps
+    //      of the last group reach up to 11 doubles past the last one).  Per output the taps are still accumulated in ascending order, so the result is
     //      bit-identical to the plain loop.
     double acc = 0.0;
     if (VP_ABL(ABL_NOCHI) && OUT == 0) { VP_STAMP(4); return fl[tid]; }
