@@ -174,6 +174,32 @@ int vp_model_flux_batch_device(vp_ctx* ctx, int inst, int W, int D, const double
  * line l, UNCONVOLVED -- exactly what the reference returns despite its comment (SURVEY trap T11). */
 int vp_model_flux_components(vp_ctx* ctx, int inst, int W, int D, const double* theta, double* out);
 
+/* lnprob AND its analytic gradient d lnprob / d theta for a batch of walker rows: lnprob is (W), grad is row-major (W, D),
+ * host memory.  Replaces: the serial finite differences scipy.optimize.minimize forms around the reference's objective
+ * (vfit_mcmc.py:355-360 and quick_fit_interface.py:56-63: D+1 model evaluations per gradient, and a forward difference of a
+ * staircase -- x is the difference of two frequencies of order 1e15).  The gradient is computed in reverse mode, in fp64, on the
+ * GPU: lnprob by the launches of vp_lnprob_batch_device, then the unconvolved flux, the adjoint of the edge-replicated LSF
+ * convolution and one more walk over the lines with H and L = Im w; its cost does not depend on D.  No atomics: a row's
+ * bits depend on that row alone (not on the batch it is in, nor on the call).
+ * Rows without a gradient: a row outside the box or with a NaN in theta gets the lnprob vp_lnprob_batch gives it (-inf / NaN)
+ * and a gradient row of NaN, and no model is evaluated for it; a row inside the box whose lnlike is -inf or NaN (error = 0
+ * pixels and the like) gets a NaN gradient row too.  Finite rows next to such rows are unaffected.  The prior is a box: it
+ * adds nothing inside.
+ * Refused in this version, with VP_EINVAL and a vp_last_error text (never a fallback): instruments added with
+ * VP_VOIGT_FAST (piecewise, bug-compatible formula) and instruments whose wavelength array holds NaN samples (astropy's
+ * NaN interpolation has no useful adjoint).  There is no vp_multi_*, sampler or gather form of these entries, and the Python
+ * consumers refuse host-callable instruments. */
+int vp_lnprob_grad_batch(vp_ctx* ctx, int W, int D, const double* theta, double* lnprob, double* grad);
+
+/* Same, operands already resident on the context's GPU; enqueued on `hip_stream` (NULL = the context's own stream) and NOT
+ * synchronised, like vp_lnprob_batch_device.  Same bits as the host entry. */
+int vp_lnprob_grad_batch_device(vp_ctx* ctx, int W, int D, const double* d_theta, double* d_lnprob, double* d_grad,
+                                void* hip_stream);
+
+/* w(x_j + i a_i) = H + i L on the device for a grid (host buffers; H and L are row-major (na, nx)).  Test hook, like
+ * vp_voigt_h, for the complex tiers of the gradient kernels (tier chosen per wavefront = 64 consecutive x_j of one a_i). */
+int vp_voigt_w(vp_ctx* ctx, int na, const double* a, int nx, const double* x, double* H, double* L);
+
 /* H(a_i, x_j) = Re w(x_j + i a_i) on the device for a grid (host buffers; out is row-major
  * (na, nx)).  Test hook for the Faddeeva tiers that replace scipy.special.wofz at the call site
  * core/voigt_model.py:156: the production tier logic is used (tier chosen per wavefront = 64
@@ -333,7 +359,7 @@ const char* vp_last_error(const vp_ctx* ctx);
 
 /* Library version string: "rbvfit_amd " RBVFIT_AMD_VERSION " (gfx950, hip)".  One number for the header, the library and the
  * Python package (rbvfit_amd.__version__); tests/test_cabi_symbols.py checks that they agree. */
-#define RBVFIT_AMD_VERSION "0.4.0"
+#define RBVFIT_AMD_VERSION "0.5.0"
 const char* vp_version(void);
 
 #ifdef __cplusplus

@@ -11,6 +11,7 @@
 //   capi_samplers.inc     vp_stretch_run, vp_slice_run
 //   capi_multi.inc        vp_multi_* (several device contexts, one process)
 //   capi_misc.inc         test hooks, timing, introspection
+//   capi_grad.inc         vp_lnprob_grad_batch* (analytic gradient, grad_kernels.h), vp_voigt_w
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,6 +32,7 @@
 #include "voigt_kernels.h"
 #include "sampler_kernels.h"
 #include "slice_kernels.h"
+#include "grad_kernels.h"
 
 #include "capi_context.inc"
 #include "capi_launch.inc"
@@ -44,5 +46,6 @@ extern "C" {
 #include "capi_samplers.inc"
 #include "capi_multi.inc"
 #include "capi_misc.inc"
+#include "capi_grad.inc"
 
 }  // extern "C"

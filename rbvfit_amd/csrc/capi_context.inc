@@ -243,6 +243,15 @@ struct vp_ctx {
         int* peer_flags[vp::MAX_REPLICAS] = {};
     } gather;
     const vp::Replicas* gather_rep = nullptr;   // set around an enqueue_lnprob whose results go into the ranks' gathered vectors
+    // workspace of the gradient path (vp_lnprob_grad_batch*, capi_grad.inc), grown on demand; sizes in doubles
+    struct Grad {
+        double* fl = nullptr;     // (rows, P) unconvolved flux, then s = d lnL / d tau_total
+        double* q = nullptr;      // (rows, P) d lnL / d model
+        double* rec = nullptr;    // (rows, L, LC_STRIDE) line records
+        double* part = nullptr;   // (rows, L, chunks, 3) partial sums of the lines
+        double* io = nullptr;     // host entry: theta | grad | lnprob
+        size_t n_fl = 0, n_q = 0, n_rec = 0, n_part = 0, n_io = 0;
+    } grad;
     // model_flux / voigt_h scratch
     double* d_scratch = nullptr;
     size_t scratch_bytes = 0;

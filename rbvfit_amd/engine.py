@@ -293,6 +293,36 @@ class Engine:
         self._check(self._lib.vp_voigt_h(self._ctx, a.size, _dp(a), x.size, _dp(x), _dp(out)))
         return out
 
+    def voigt_w(self, a, x):
+        """(H, L) = (Re, Im) w(x_j + i a_i) grids on the device (test hook for the complex tiers of the gradient kernels)."""
+        self._guard()
+        a, x = _f64(a).ravel(), _f64(x).ravel()
+        H = np.empty((a.size, x.size), dtype=np.float64)
+        L = np.empty((a.size, x.size), dtype=np.float64)
+        self._check(self._lib.vp_voigt_w(self._ctx, a.size, _dp(a), x.size, _dp(x), _dp(H), _dp(L)))
+        return H, L
+
+    # -- analytic gradient (vp_lnprob_grad_batch) --------------------------------------------------
+    def lnprob_grad(self, theta):
+        """(W, D) host array -> (lnprob (W,), grad (W, D)): lnprob and its analytic gradient, reverse mode on the GPU.
+        Rows whose lnprob is not finite (outside the box, NaN in theta, lnlike -inf / NaN) get a NaN gradient row.
+        Raises ``RbvfitAmdError`` for instruments with ``voigt_method='fast'`` or NaN wavelength samples."""
+        self._guard()
+        th = self._theta2d(theta)
+        W = th.shape[0]
+        lnp = np.empty(W, dtype=np.float64)
+        grad = np.empty((W, self.ndim), dtype=np.float64)
+        self._check(self._lib.vp_lnprob_grad_batch(self._ctx, W, th.shape[1], _dp(th) if W else None, _dp(lnp) if W else None,
+                                                   _dp(grad) if W else None))
+        return lnp, grad
+
+    def lnprob_grad_device(self, d_theta_ptr: int, d_lnprob_ptr: int, d_grad_ptr: int, W: int, stream_ptr: int = 0):
+        """Device-resident operands (raw pointers: theta (W, D), lnprob (W), grad (W, D)); asynchronous on ``stream_ptr``
+        like ``lnprob_device``."""
+        self._guard()
+        self._check(self._lib.vp_lnprob_grad_batch_device(self._ctx, int(W), self.ndim, C.c_void_p(d_theta_ptr),
+                                                          C.c_void_p(d_lnprob_ptr), C.c_void_p(d_grad_ptr), C.c_void_p(stream_ptr)))
+
     # -- device-resident ensemble sampler (vp_stretch_run) ---------------------------------------
     def stretch_run(self, pos, nsteps: int, lnprob=None, a: float = 2.0, seed: int = 0, step0: int = 0,
                     store_chain: bool = True, naccepted=None):

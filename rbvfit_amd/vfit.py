@@ -230,19 +230,41 @@ class vfit:
         lp = self.lnprob(batch)
         return float(lp[0]), (lp[1:] - lp[0]) / h
 
-    def optimize_guess(self, theta, eps: float = 1e-8):
+    def lnprob_grad(self, theta):
+        """lnprob and its ANALYTIC gradient (``Engine.lnprob_grad``: reverse mode on the GPU, cost independent of D).
+        (D,) -> (float, (D,)); (W, D) -> ((W,), (W, D)).  Rows whose lnprob is not finite get a NaN gradient row.
+        Host-callable instruments have no analytic gradient: refused."""
+        if self._host_instruments:
+            raise NotImplementedError("lnprob_grad: host-callable instruments have no analytic gradient (use grad='fd')")
+        th = np.asarray(theta, dtype=np.float64)
+        lp, g = self.engine.lnprob_grad(np.atleast_2d(th))
+        return (float(lp[0]), g[0]) if th.ndim == 1 else (lp, g)
+
+    # L-BFGS-B with the analytic gradient: scipy's default ftol (2.2e-9 relative, i.e. ~2e-5 on an lnprob of 1e4) is sized for
+    # finite-difference slopes; an exact gradient lets the search go on to where the slope itself vanishes
+    _ANALYTIC_OPTIONS = {"ftol": 1e-12, "gtol": 1e-8}
+
+    @staticmethod
+    def _grad_mode(grad):
+        if grad not in ("fd", "analytic"):
+            raise ValueError(f"grad must be 'fd' or 'analytic'; got {grad!r}")
+        return grad == "analytic"
+
+    def optimize_guess(self, theta, eps: float = 1e-8, grad: str = "fd"):
         """Mirror of ``vfit.optimize_guess`` (vfit_mcmc.py:355-360): L-BFGS-B on -lnprob inside the
-        bounds, with the finite-difference gradient evaluated as one GPU batch per iteration."""
+        bounds, with the finite-difference gradient evaluated as one GPU batch per iteration
+        (``grad='fd'``, the default) or the analytic gradient of ``lnprob_grad`` (``grad='analytic'``)."""
         import scipy.optimize as op
+        analytic = self._grad_mode(grad)
 
         def nll(th):
-            f, g = self.lnprob_and_grad(th, eps)
+            f, g = self.lnprob_grad(th) if analytic else self.lnprob_and_grad(th, eps)
             if not np.isfinite(f):
                 return np.inf, np.zeros_like(th)
             return -f, -g
 
         res = op.minimize(nll, np.asarray(theta, dtype=np.float64), jac=True, method="L-BFGS-B",
-                          bounds=list(zip(self.lb, self.ub)))
+                          bounds=list(zip(self.lb, self.ub)), options=self._ANALYTIC_OPTIONS if analytic else None)
         return res.x
 
     # -- quick fit (SURVEY 3.4 / 8f N2) --------------------------------------------------------------
@@ -270,17 +292,32 @@ class vfit:
             err = np.where(d2 > 0, np.sqrt(1.0 / d2), np.abs(tb - ti))
         return err
 
-    def fit_quick(self, verbose: bool = False, eps: float = 1e-8):
+    def fit_quick(self, verbose: bool = False, eps: float = 1e-8, grad: str = "fd"):
         """Mirror of ``vfit.fit_quick`` (vfit_mcmc.py:362-406 -> quick_fit_interface.py:10-84):
         L-BFGS-B on chi2 inside the bounds (``maxfun=5000``), then curvature errors.  The
         finite-difference gradient scipy would build serially is one (D+1)-row GPU batch per
-        iteration.  Returns (theta_best, theta_best_error) and stores them on the object."""
+        iteration (``grad='fd'``, the default); ``grad='analytic'`` takes chi2 and its gradient from
+        ``lnprob_grad`` instead (chi2 = -2 lnlike + sum log w, so its gradient is -2 x the lnlike gradient;
+        inside the bounds the box prior adds nothing).  Returns (theta_best, theta_best_error) and
+        stores them on the object."""
         import warnings
         import scipy.optimize as op
         self.mcmc_flag = False
         lb, ub = self.lb, self.ub
+        analytic = self._grad_mode(grad)
+        if analytic and self._host_instruments:
+            raise NotImplementedError("fit_quick: host-callable instruments have no analytic gradient (use grad='fd')")
+        const = sum(float(np.sum(np.asarray(e["log_inv_sigma2"], dtype=np.float64))) for e in self.instrument_data.values())
+
+        def objective_analytic(th):
+            lp, g = self.lnprob_grad(th)
+            if not (np.isfinite(lp) and np.all(np.isfinite(g))):
+                return 1e10, np.zeros_like(th)               # quick_fit_interface.py:51-53
+            return -2.0 * lp + const, -2.0 * g
 
         def objective(th):
+            if analytic:
+                return objective_analytic(th)
             h = np.where(th + eps > ub, -eps, eps)
             c = self.chi2(np.vstack([th[None, :], th[None, :] + np.diag(h)]))
             if not np.all(np.isfinite(c)):
@@ -289,7 +326,7 @@ class vfit:
 
         try:
             res = op.minimize(objective, np.asarray(self.theta, dtype=np.float64), jac=True, method="L-BFGS-B",
-                              bounds=list(zip(lb, ub)), options={"maxfun": 5000})
+                              bounds=list(zip(lb, ub)), options=dict({"maxfun": 5000}, **(self._ANALYTIC_OPTIONS if analytic else {})))
             theta_best = res.x
             theta_err = self.estimate_parameter_errors(theta_best, self.theta)
             if not res.success:
