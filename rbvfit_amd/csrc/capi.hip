@@ -3,7 +3,7 @@
 //
 // ONE translation unit (the kernels are templates in headers; every instance is compiled once), laid out by concern:
 //   capi_context.inc      Tuning knobs, Instrument, vp_ctx / vp_multi, workspace
-//   capi_launch.inc       launch policy: which kernels a batch gets, enqueue_lnprob
+//   capi_launch.inc       launch policy: which kernels a batch gets (plan_lnprob) and their launches (enqueue_plan), enqueue_lnprob
 //   capi_prearm.inc       pre-armed launches, the registry of live contexts
 //   capi_setup.inc        vp_ctx_create ... vp_add_instrument, vp_lnprob_batch_device
 //   capi_gather.inc       vp_gather_* (direct-write gather between ranks)

@@ -256,8 +256,6 @@ struct vp_ctx {
     double* d_scratch = nullptr;
     size_t scratch_bytes = 0;
     // optional per-kernel timing with HIP events on the launch stream (bench.py roofline leg)
-    int policy_W = 0;            // > 0: the launch structure of a batch is chosen as for THIS many rows (a block of a larger batch
-                                 // that other contexts share: same structure, hence the same bits, as the whole batch on one context)
     int last_kind = 0;           // launch structure of the last lnprob batch: 0 prep + tile (+ finalize), 1 walker_kernel
     int last_split = 0;          // ... and, for walker_kernel, the workgroups per walker of its split form (0: the ordinary form)
     // the far-field expansions the last lnprob batch made for its FIRST instrument that took any (vp_last_farfield_info):

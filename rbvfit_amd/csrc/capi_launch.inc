@@ -1,58 +1,59 @@
 // capi_launch.inc -- launch policy: which kernels a batch gets (tile launches, walker_kernel and its split form, far-field expansions).
 // A fragment of the ONE translation unit capi.hip (included there, in order; not a header of its own).
+// What a tile launch may be handed beyond its positional arguments (named at the call site; one object serves the
+// GENERIC = false launch and the GENERIC = true launch behind it: each reads only its own fields)
+struct TileOpts {
+    const vp::InstDev* geom = nullptr;          // the launch's geometry where it is not in.dev
+    int grid_z = 1;                             // (components: the line as a grid dimension)
+    double* ff = nullptr;                       // GENERIC = false: far lines from the blocks' expansions
+    int gen_slots = 0;                          // GENERIC = true: > 0, a grid of at most this many workgroups per tile walks the flagged walkers
+    const double* theta_rebuild = nullptr;      // GENERIC = true behind walker_kernel's flux form: whole records are formed first, from D parameters a row
+    int D = 0;
+};
 template <int OUT, bool GENERIC>
 void launch_tile(const Instrument& in, const double* lc, const int* flags, double* out, int stride, int offset,
-                 int W, hipStream_t s, const vp::FinalizeArgs& fin, const int* genflag, const vp::InstDev* geom = nullptr,
-                 int grid_z = 1, double* ff = nullptr, int gen_slots = 0, const double* theta_rebuild = nullptr, int D = 0) {
-    const vp::InstDev& dev = geom ? *geom : in.dev;
-    dim3 grid(W, dev.ntiles, grid_z);
+                 int W, hipStream_t s, const vp::FinalizeArgs& fin, const int* genflag, const TileOpts& o = TileOpts{}) {
+    const vp::InstDev& dev = o.geom ? *o.geom : in.dev;
+    const bool fast = dev.method == VP_VOIGT_FAST;
+    dim3 grid(W, dev.ntiles, o.grid_z);
     dim3 block(64 * in.nwaves);
+    // (almost always an empty launch: a small grid whose workgroups walk the flagged walkers -- tile_generic_kernel)
+    //  where the batch before flagged none; one workgroup per walker otherwise, as a fit with damped lines needs them)
+    const dim3 gg(o.gen_slots > 0 ? std::min(W, o.gen_slots) : W, dev.ntiles, o.grid_z);
     if (dev.rbot && OUT != 2) {           // NaN wavelength samples on the astropy branch: the instances that renormalise (InstDev::rbot)
         constexpr int O = OUT == 1 ? 1 : 0;
-        if (GENERIC) {
-            const dim3 gg(gen_slots > 0 ? std::min(W, gen_slots) : W, dev.ntiles, grid_z);
+        if (GENERIC)
             hipLaunchKernelGGL((vp::tile_generic_kernel<O, false, true>), gg, block, in.lds_bytes, s, dev, lc, flags, out, stride, offset, fin, genflag, W,
                                in.lines, (const double*)nullptr, 0);
-        } else if (dev.method == VP_VOIGT_FAST) {
-            hipLaunchKernelGGL((vp::tile_kernel<1, O, false, false, true>), grid, block, in.lds_bytes, s, dev, lc, flags, out, stride, offset, fin, genflag);
-        } else {
-            hipLaunchKernelGGL((vp::tile_kernel<0, O, false, false, true>), grid, block, in.lds_bytes, s, dev, lc, flags, out, stride, offset, fin, genflag);
-        }
+        else
+            hipLaunchKernelGGL((fast ? vp::tile_kernel<1, O, false, false, true> : vp::tile_kernel<0, O, false, false, true>), grid, block, in.lds_bytes, s,
+                               dev, lc, flags, out, stride, offset, fin, genflag);
         return;
     }
 #ifndef VP_NO_TILE1
-    if (OUT == 0 && !GENERIC && in.nwaves == 1 && grid_z == 1) {        // single-wave tiles: the kernel compiled for them alone
+    if (OUT == 0 && !GENERIC && in.nwaves == 1 && o.grid_z == 1) {        // single-wave tiles: the kernel compiled for them alone
         vp::Tile1Args a{dev, lc, flags, genflag, vp::TileTail{out, stride, offset, fin}};
-        a.I.ff = ff;
-        if (dev.method == VP_VOIGT_FAST) hipLaunchKernelGGL((vp::tile_kernel1<1, false>), grid, block, in.lds_bytes, s, a);
-        else if (ff) hipLaunchKernelGGL((vp::tile_kernel1<0, true>), grid, block, in.lds_bytes, s, a);
-        else hipLaunchKernelGGL((vp::tile_kernel1<0, false>), grid, block, in.lds_bytes, s, a);
+        a.I.ff = o.ff;
+        hipLaunchKernelGGL((fast ? vp::tile_kernel1<1, false> : o.ff ? vp::tile_kernel1<0, true> : vp::tile_kernel1<0, false>), grid, block, in.lds_bytes, s, a);
         return;
     }
 #endif
-    if (ff && OUT != 2 && !GENERIC && dev.method == VP_VOIGT_WOFZ) {     // far lines from the blocks' expansions
+    if (o.ff && OUT != 2 && !GENERIC && dev.method == VP_VOIGT_WOFZ) {     // far lines from the blocks' expansions
         vp::InstDev d2 = dev;
-        d2.ff = ff;
+        d2.ff = o.ff;
         hipLaunchKernelGGL((vp::tile_kernel<0, OUT == 1 ? 1 : 0, false, true>), grid, block, in.lds_bytes, s, d2, lc, flags, out, stride, offset, fin, genflag);
         return;
     }
-    if (dev.method == VP_VOIGT_FAST) {
-        if (!GENERIC)
-            hipLaunchKernelGGL((vp::tile_kernel<1, OUT, false>), grid, block, in.lds_bytes, s, dev, lc, flags, out,
-                               stride, offset, fin, genflag);
-    } else if (GENERIC) {
-        // (almost always an empty launch: a small grid whose workgroups walk the flagged walkers -- tile_generic_kernel)
-        //  where the batch before flagged none; one workgroup per walker otherwise, as a fit with damped lines needs them)
-        const dim3 gg(gen_slots > 0 ? std::min(W, gen_slots) : W, dev.ntiles, grid_z);
-        if (OUT == 1 && theta_rebuild)
+    if (!GENERIC) {
+        hipLaunchKernelGGL((fast ? vp::tile_kernel<1, OUT, false> : vp::tile_kernel<0, OUT, false>), grid, block, in.lds_bytes, s, dev, lc, flags, out,
+                           stride, offset, fin, genflag);
+    } else if (!fast) {
+        if (OUT == 1 && o.theta_rebuild)
             hipLaunchKernelGGL((vp::tile_generic_kernel<1, true>), gg, block, in.lds_bytes, s, dev, lc, flags, out, stride, offset, fin, genflag, W,
-                               in.lines, theta_rebuild, D);
+                               in.lines, o.theta_rebuild, o.D);
         else
             hipLaunchKernelGGL((vp::tile_generic_kernel<OUT, false>), gg, block, in.lds_bytes, s, dev, lc, flags, out, stride, offset, fin, genflag, W,
                                in.lines, (const double*)nullptr, 0);
-    } else {
-        hipLaunchKernelGGL((vp::tile_kernel<0, OUT, false>), grid, block, in.lds_bytes, s, dev, lc, flags, out,
-                           stride, offset, fin, genflag);
     }
 }
 
@@ -80,9 +81,6 @@ size_t prof_mark(vp_ctx* c, hipStream_t s) {
     return i;
 }
 
-// enqueue the whole lnprob pipeline for device-resident theta / out: per instrument a prep launch
-// (line records; the first one also applies the box prior and writes -inf rows) and a tile launch;
-// the last-arriving tile workgroup of each walker performs the final reduction.
 // Record preparation launch: one lane per record, 64 records per wave (fewer per wave measured no
 // faster even at 512 walkers x 4 lines; the prep_rpw knob overrides for experiments).
 // The generic-path flags of a record-preparation launch: the buffer whose turn it is, zero in its first W entries (a memset only
@@ -108,8 +106,7 @@ static int genflag_acquire(vp_ctx* c, int W, hipStream_t s, GenFlags* out) {
     *out = GenFlags{use, c->d_genflag + (size_t)o * c->capW, c->h_gen_any_dev, nullptr, quiet ? vp::GEN_SLOTS : 0};
     return VP_OK;
 }
-static void launch_prep(const vp_ctx* c, const Instrument& in, const double* d_theta, int W, int do_flags, double* d_out,
-                        int* genflag, hipStream_t s, int* genflag_clear = nullptr, int* gen_any = nullptr, int* gen_any_clear = nullptr) {
+static void launch_prep(const vp_ctx* c, const Instrument& in, const double* d_theta, int W, int do_flags, double* d_out, const GenFlags& gf, hipStream_t s) {
     const long nline = (long)W * in.dev.L, ncl = (long)W * in.dev.NCm;
     const int rpw = std::max(1, std::min(64, c->tune.prep_rpw));
     vp::PrepGrid g;
@@ -125,7 +122,7 @@ static void launch_prep(const vp_ctx* c, const Instrument& in, const double* d_t
     // (direct-write gather: the pass's first launch -- the one that applies the box prior -- handshakes with the peers)
     const vp::Replicas rep = (c->gather_rep && do_flags) ? *c->gather_rep : vp::Replicas{};
     hipLaunchKernelGGL(vp::prep_lines_kernel, dim3(g.nb_line + g.nb_cl + g.nb_flag), dim3(64), 0, s, d_theta, W, c->D,
-                       in.lines, c->d_lb, c->d_ub, c->d_lc, c->d_flags, do_flags, d_out, genflag, g, rep, genflag_clear, gen_any, gen_any_clear);
+                       in.lines, c->d_lb, c->d_ub, c->d_lc, c->d_flags, do_flags, d_out, gf.use, g, rep, gf.clear, gf.any, gf.any_clear);
 }
 
 // walker_kernel: the whole batch in ONE launch (workgroup = walker, wave = tile).  Possible for a single
@@ -151,9 +148,10 @@ size_t walker_wave_lds(const vp_ctx* c) {
     for (auto& in : c->inst) b = std::max(b, in.lds_w);
     return b;
 }
-size_t walker_lds_bytes(const vp_ctx* c) {           // tiles | tile sums, prior flag, spare | sampler form: 4 scalars, X_k, Y (64 each)
-    return (size_t)walker_tiles(c) * walker_wave_lds(c) + (walker_tiles(c) + 2 + 4 + 128) * sizeof(double);
+size_t walker_lds(int waves, size_t wave_lds) {      // tiles | tile sums, prior flag, spare | sampler form: 4 scalars, X_k, Y (64 each)
+    return (size_t)waves * wave_lds + (size_t)(waves + 2 + 4 + 128) * sizeof(double);
 }
+size_t walker_lds_bytes(const vp_ctx* c) { return walker_lds(walker_tiles(c), walker_wave_lds(c)); }
 
 #ifndef VP_WALKER_MAX_LINES
 #define VP_WALKER_MAX_LINES 40        // above: the launches win (multipoles, far-field expansions, finer scheduling) -- 5000 pixels,
@@ -192,7 +190,6 @@ bool walker_applies(const vp_ctx* c, int W) {
     return layers <= per_cu && (layers <= 3 || layers <= per_cu - 2);
 }
 
-int walker_prio_for(vp_ctx* c, int W);
 int ctx_num_cus(vp_ctx* c) {
     if (c->num_cus == 0) {
         int n = 0;
@@ -224,37 +221,33 @@ int walker_split_for(vp_ctx* c, int W) {
     if (G < 2 || (long)W * G > 1024) return 0;
     const int nwpg = (nt + G - 1) / G;
     if (nwpg > vp::WALKER_THREADS_MAX / 64) return 0;
-    if ((size_t)nwpg * in.lds_s + (size_t)(nwpg + 2 + 4 + 128) * sizeof(double) > c->lds_limit) return 0;
+    if (walker_lds(nwpg, in.lds_s) > c->lds_limit) return 0;
     return G;
 }
 struct SplitShape { int G, waves; size_t lds; };
 SplitShape split_shape(const vp_ctx* c, int G) {
     const Instrument& in = c->inst[0];
     const int nwpg = (in.dev_s.ntiles + G - 1) / G;
-    return SplitShape{G, nwpg, (size_t)nwpg * in.lds_s + (size_t)(nwpg + 2 + 4 + 128) * sizeof(double)};
+    return SplitShape{G, nwpg, walker_lds(nwpg, in.lds_s)};
 }
 
 // (clusters: without their multipole records the members are ordinary lines -- a few more wing evaluations per pass
 // against a cluster preparation chain inside every workgroup)
-// split > 0: the split form -- W x split workgroups on the one-pass geometry; split_row0: first row of the tile-sum / ticket
+// a.split > 0: the split form -- W x split workgroups on the one-pass geometry; a.split_row0: first row of the tile-sum / ticket
 // workspace this launch may use (the record rows come with a.lc)
 template <bool SAMPLER, bool ARMED = false>
-void launch_walker_any(vp_ctx* c, int W, vp::WalkerArgs a, const vp::StretchArgs& st, hipStream_t s, int split = 0, int split_row0 = 0) {
+void launch_walker_any(vp_ctx* c, int W, const vp::WalkerArgs& a, const vp::StretchArgs& st, hipStream_t s) {
     const Instrument& in = c->inst[0];
-    if (split > 0) {
-        const SplitShape sh = split_shape(c, split);
+    const bool fast = in.dev.method == VP_VOIGT_FAST;
+    if (a.split > 0) {
+        const SplitShape sh = split_shape(c, a.split);
         vp::InstDev d0 = in.dev_s;
         vp::LinesDev t0 = in.lines;
         d0.NCm = 0; t0.NCm = 0;
         d0.core_hint = in.split_hint;
         d0.ff = nullptr;
-        a.wave_lds = (int)(in.lds_s / sizeof(double));
-        a.split = split; a.split_row0 = split_row0; a.split_part = c->d_partial; a.split_ticket = c->d_ticket;
-        a.wperm = 0xFEDCBA9876543210ull;
-        if (!SAMPLER) a.prio = walker_prio_for(c, W * split);
-        const dim3 grid(W * split), block(64 * sh.waves);
-        if (in.dev.method == VP_VOIGT_FAST) hipLaunchKernelGGL((vp::walker_kernel<1, false, SAMPLER, ARMED, 0, true>), grid, block, sh.lds, s, d0, t0, a, st);
-        else hipLaunchKernelGGL((vp::walker_kernel<0, false, SAMPLER, ARMED, 0, true>), grid, block, sh.lds, s, d0, t0, a, st);
+        hipLaunchKernelGGL((fast ? vp::walker_kernel<1, false, SAMPLER, ARMED, 0, true> : vp::walker_kernel<0, false, SAMPLER, ARMED, 0, true>),
+                           dim3(W * a.split), dim3(64 * sh.waves), sh.lds, s, d0, t0, a, st);
         return;
     }
     const dim3 grid(W), block(64 * walker_tiles(c));
@@ -275,19 +268,16 @@ void launch_walker_any(vp_ctx* c, int W, vp::WalkerArgs a, const vp::StretchArgs
             tsum += dk[k].ntiles;
         }
         for (size_t k = c->inst.size(); k < 4; ++k) tb.t[k - 1] = tsum;        // (no tiles)
-        const bool fast = in.dev.method == VP_VOIGT_FAST;
-        if (c->inst.size() == 2) {
-            if (fast) hipLaunchKernelGGL((vp::walker_kernel2<1, SAMPLER, ARMED>), grid, block, lds, s, dk[0], dk[1], tb, t0, a, st);
-            else hipLaunchKernelGGL((vp::walker_kernel2<0, SAMPLER, ARMED>), grid, block, lds, s, dk[0], dk[1], tb, t0, a, st);
-        } else {
-            if (fast) hipLaunchKernelGGL((vp::walker_kernel4<1, SAMPLER, ARMED>), grid, block, lds, s, dk[0], dk[1], dk[2], dk[3], tb, t0, a, st);
-            else hipLaunchKernelGGL((vp::walker_kernel4<0, SAMPLER, ARMED>), grid, block, lds, s, dk[0], dk[1], dk[2], dk[3], tb, t0, a, st);
-        }
+        if (c->inst.size() == 2)
+            hipLaunchKernelGGL((fast ? vp::walker_kernel2<1, SAMPLER, ARMED> : vp::walker_kernel2<0, SAMPLER, ARMED>), grid, block, lds, s, dk[0], dk[1], tb, t0, a, st);
+        else
+            hipLaunchKernelGGL((fast ? vp::walker_kernel4<1, SAMPLER, ARMED> : vp::walker_kernel4<0, SAMPLER, ARMED>), grid, block, lds, s, dk[0], dk[1], dk[2], dk[3],
+                               tb, t0, a, st);
         return;
     }
-    if (in.dev.method == VP_VOIGT_FAST) hipLaunchKernelGGL((vp::walker_kernel<1, false, SAMPLER, ARMED>), grid, block, lds, s, d0, t0, a, st);
-    else if (keep_clusters) hipLaunchKernelGGL((vp::walker_kernel<0, true, false, ARMED>), grid, block, lds, s, d0, t0, a, st);
-    else hipLaunchKernelGGL((vp::walker_kernel<0, false, SAMPLER, ARMED>), grid, block, lds, s, d0, t0, a, st);
+    hipLaunchKernelGGL((fast ? vp::walker_kernel<1, false, SAMPLER, ARMED> : keep_clusters ? vp::walker_kernel<0, true, false, ARMED>
+                                                                                            : vp::walker_kernel<0, false, SAMPLER, ARMED>),
+                       grid, block, lds, s, d0, t0, a, st);
 }
 
 // which deal of tiles to waves a walker launch of W workgroups gets (Tuning::walker_perm)
@@ -296,26 +286,47 @@ unsigned long long walker_perm_for(vp_ctx* c, int W) {
     if (c->inst.size() != 1 || c->tune.walker_perm == 0) return ident;
     if (c->tune.walker_perm_hex != 0) return (unsigned long long)c->tune.walker_perm_hex;     // (experiments: an explicit deal)
     if (c->tune.walker_perm > 0) return c->inst[0].wperm;
-    if (c->num_cus == 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess) c->num_cus = n;
-    }
-    return (c->num_cus > 0 && W <= c->num_cus) ? c->inst[0].wperm : ident;
+    return (ctx_num_cus(c) > 0 && W <= ctx_num_cus(c)) ? c->inst[0].wperm : ident;
 }
 // raised issue priority for the waves with line cores: where workgroups share a CU (WalkerArgs::prio)
 int walker_prio_for(vp_ctx* c, int W) {
     if (c->tune.walker_prio >= 0) return c->tune.walker_prio ? 1 : 0;
-    if (c->num_cus == 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess) c->num_cus = n;
-    }
-    return (c->num_cus > 0 && W <= c->num_cus) ? 0 : 1;
+    return (ctx_num_cus(c) > 0 && W <= ctx_num_cus(c)) ? 0 : 1;
 }
 
-void launch_walker(vp_ctx* c, int W, const double* d_theta, double* d_out, hipStream_t s, const vp::Replicas* gather = nullptr,
-                   bool armed = false) {
-    vp::WalkerArgs a{d_theta, c->d_lb, c->d_ub, c->d_lc, d_out, c->inst[0].sum_logw, c->D, (int)(walker_wave_lds(c) / sizeof(double)),
-                     walker_prio_for(c, W), walker_perm_for(c, W)};
+// The WalkerArgs of every form of the launch: W walkers that read `theta` and write `out` (both nullptr in the sampler form, whose
+// rows come with StretchArgs); split > 0: the split form, W x split workgroups whose rows of the tile-sum / ticket workspace begin at
+// row0 -- every workgroup of a walker has its own record rows, so a second launch in flight starts behind row0 x split of them;
+// shared_cus: another launch sits on the CUs at the same time (overlapped half-steps)
+vp::WalkerArgs walker_args(vp_ctx* c, int W, const double* theta, double* out, double sum_logw, int split = 0, int row0 = 0,
+                           bool shared_cus = false) {
+    const Instrument& in = c->inst[0];
+    const size_t nrec = (size_t)(in.dev.L + in.dev.NCm) * vp::LC_STRIDE;
+    const int per = std::max(1, split);
+    vp::WalkerArgs a{theta, c->d_lb, c->d_ub, c->d_lc + (size_t)row0 * per * nrec, out, sum_logw, c->D,
+                     (int)((split > 0 ? in.lds_s : walker_wave_lds(c)) / sizeof(double)),
+                     (shared_cus && c->tune.walker_prio < 0) ? 1 : walker_prio_for(c, W * per),     // (overlapped half-steps share the CUs)
+                     split > 0 ? 0xFEDCBA9876543210ull : walker_perm_for(c, W)};
+    if (split > 0) { a.split = split; a.split_row0 = row0; a.split_part = c->d_partial; a.split_ticket = c->d_ticket; }
+    return a;
+}
+
+// What a batch gets, decided once (plan_lnprob) and then launched as decided (enqueue_plan); record_launch keeps what the
+// introspection calls report.
+struct LaunchPlan {
+    int kind = 0;            // vp_last_launch_kind: 0 prep + tile (+ finalize) launches, 1 walker_kernel, 2 the launches with far-field expansions,
+                             // 3 all instruments' tiles in one launch (tile_kernel_multi); < 0: not an lnprob batch (model flux)
+    int split = 0;           // walker_kernel: workgroups per walker of its split form (0: the ordinary form)
+    int Wp = 0;              // rows the structure is chosen for
+    int sel = 0;             // geometry of the tile launches: 0 full-size tiles (Instrument::dev), 1 one-pass tiles (dev_s), 2 single-wave tiles (dev_w)
+    int fmode = 0;           // final reduction: 0 a launch of its own, 1 by ticket in the tile kernel
+    int ff_first = -1;       // first instrument that takes far-field expansions (ff_wanted answers for the others) ...
+    int ff_first_blk = 0;    // ... and the blocks per row that the instruments before it have in the workspace
+};
+const vp::InstDev& geom_of(const Instrument& x, int sel) { return sel == 2 ? x.dev_w : sel ? x.dev_s : x.dev; }
+
+void launch_walker(vp_ctx* c, const LaunchPlan& p, int W, const double* d_theta, double* d_out, hipStream_t s, bool armed = false) {
+    vp::WalkerArgs a = walker_args(c, W, d_theta, d_out, c->inst[0].sum_logw, p.split);
     if (armed) {
         a.arm_slots = c->arm.slots;
         a.arm_slot_doubles = c->arm.slot_doubles;
@@ -329,11 +340,9 @@ void launch_walker(vp_ctx* c, int W, const double* d_theta, double* d_out, hipSt
         a.arm_ticks = 100 * c->arm.budget_us;
     }
     vp::StretchArgs st{};
-    if (gather) st.rep = *gather;            // (the plain form's only use of the sampler arguments: where the results go)
-    const int split = gather ? 0 : walker_split_for(c, c->policy_W > 0 ? c->policy_W : W);
-    c->last_split = split;
-    if (armed) launch_walker_any<false, true>(c, W, a, st, s, split);
-    else launch_walker_any<false>(c, W, a, st, s, split);
+    if (c->gather_rep) st.rep = *c->gather_rep;      // (the plain form's only use of the sampler arguments: where the results go)
+    if (armed) launch_walker_any<false, true>(c, W, a, st, s);
+    else launch_walker_any<false>(c, W, a, st, s);
 }
 
 // One stretch-move half-step of the active half (nS walkers) as ONE launch: proposal, lnprob and accept/reject inside
@@ -341,30 +350,187 @@ void launch_walker(vp_ctx* c, int W, const double* d_theta, double* d_out, hipSt
 // (lc_row0: first row of the record workspace this launch may use -- two half-steps in flight at once, vp_stretch_run's
 //  overlapped form, must not share rows)
 void launch_walker_stretch(vp_ctx* c, int nS, const vp::StretchArgs& st, hipStream_t s, int lc_row0 = 0, int split = 0) {
-    const size_t nrec = (size_t)(c->inst[0].dev.L + c->inst[0].dev.NCm) * vp::LC_STRIDE;
-    if (split > 0) {        // (every workgroup of a walker has its own record rows: the second launch in flight starts behind nS x split)
-        vp::WalkerArgs a{nullptr, c->d_lb, c->d_ub, c->d_lc + (size_t)lc_row0 * split * nrec, nullptr, c->inst[0].sum_logw, c->D, 0,
-                         (st.ovl && c->tune.walker_prio < 0) ? 1 : walker_prio_for(c, nS * split), 0ull};
-        launch_walker_any<true>(c, nS, a, st, s, split, lc_row0);
-        return;
-    }
-    const vp::WalkerArgs a{nullptr, c->d_lb, c->d_ub, c->d_lc + (size_t)lc_row0 * nrec, nullptr, c->inst[0].sum_logw, c->D,
-                           (int)(walker_wave_lds(c) / sizeof(double)),
-                           (st.ovl && c->tune.walker_prio < 0) ? 1 : walker_prio_for(c, nS),     // (overlapped half-steps share the CUs)
-                           walker_perm_for(c, nS)};
-    launch_walker_any<true>(c, nS, a, st, s);
+    launch_walker_any<true>(c, nS, walker_args(c, nS, nullptr, nullptr, c->inst[0].sum_logw, split, lc_row0, st.ovl != 0), st, s);
+}
+// whole half-step in one launch (proposal, lnprob, accept inside each walker's workgroup) where the walker kernel
+// applies to a half-ensemble batch and the instrument has no cluster records
+// (vp_multi_stretch_run asks for the WHOLE half too: every context's block gets the form, hence the bits, one context gives the half)
+// returns -1 where it is not, else a walker of the half-step as several workgroups (WalkerArgs::split; 0: the ordinary form)
+int stretch_split(vp_ctx* c, int half) {
+    const bool one_launch = !c->tune.no_fused_accept && c->tune.walker != 0 && walker_applies(c, half) &&
+                            (c->inst[0].dev.NCm == 0 || !c->tune.walker_clusters);
+    return one_launch ? walker_split_for(c, half) : -1;
 }
 
-int enqueue_lnprob(vp_ctx* c, int W, const double* d_theta, double* d_out, hipStream_t s) {
-    int tile_off = 0;
+// ---- several instruments with one set of records, small batch: all their tiles in ONE launch (tile_kernel_multi)
+bool tile_multi_applies(const vp_ctx* c, int Wp) {
+    const size_t ni = c->inst.size();
+    bool multi = !c->profiling && ni >= 2 && ni <= 4 && c->tune.tile_multi != 0 && !c->tune.no_shared_prep;
+    long waves = 0;
+    for (size_t k = 0; multi && k < ni; ++k) {
+        const Instrument& in = c->inst[k];
+        if (k > 0 && !in.same_lines_as_prev) multi = false;
+        if (in.lds_w == 0 || in.dev.method != c->inst[0].dev.method || in.nanfix) multi = false;
+        if (in.needs_generic && in.dev.method == VP_VOIGT_WOFZ) multi = false;
+        waves += (long)Wp * in.dev_w.ntiles;
+    }
+    // (measured on C3, two instruments of 8192 pixels = 52 single-wave tiles per walker, us per pass, launches / one launch:
+    //  64 walkers 67.5 / 47.6, 256: 89.2 / 92.5, 512: 143.1 / 143.9, 1024: 229 / 251, 2048: 401 / 468 -- the long LSF's tiles carry
+    //  more halo as single waves, which only a batch that leaves the GPU mostly idle does not feel)
+    if (multi && c->tune.tile_multi < 0 && waves > 6144) multi = false;
+    return multi;
+}
+
+// Far-field expansions: does the extra launch pay for an instrument?
+// (the extra launch costs ~20 us; what it saves grows with walkers x blocks x lines -- measured on C2, us per pass
+// without / with: 128 walkers 54.8 / 60.5, 256 (0.42e6): 72.7 / 71.5, 512: 111.8 / 98.3, 1024: 188.8 / 153.1,
+// 2048: 349.0 / 260.5.  Below that the lines are walked directly unless "farfield" = 1 asks for the expansions.
+// What the expansions save is one evaluation per pass for every ITEM they cover (a multipole cluster or a line
+// outside clusters: C2 has 9, a 40-line FeII fit of 8 clusters 8, one of 20 lines 4), ff_cover of them (estimated
+// when the instrument is added); the crossover sits near 2e5 covered (walker, block, item) triples: C2 at 256
+// walkers (0.195e6) 72.7 / 71.5 us, the 40-line FeII fit at 1024 walkers (0.17e6) 164.9 / 161.1, the 20-line one
+// at 1024 (0.09e6) 90.4 / 93.2.
+// (round 3, after the launch itself got cheaper -- records staged in LDS, faster record preparation in front of it --: on
+//  from 1.5e5 covered triples: C2 at 256 walkers (1.95e5) 57.2 / 54.9, C4 at 64 (0.9e5) 119.5 / 130.8.)
+// (instruments that share their records come in pairs whose expansions are ONE launch: the pair's triples count together
+//  -- C3, us per pass without / with: 128 walkers 66.4 / 70.3, 256: 68.5 / 67.0, 512: 103.8 / 94.4)
+double ff_score(const Instrument& x, const vp::InstDev& gx, int Wp) {
+    return x.ff_on ? x.ff_cover * (double)Wp * gx.ntiles * gx.ff_nblk * x.ff_items : 0.0;
+}
+bool ff_pays(const vp::InstDev& gx, double score) {
+    // (instruments whose cluster members enter the expansions line by line pay more for the launch: C4 at 64 walkers
+    //  -- 1.8e5 -- 119.5 / 130.3 us, at 512 walkers 636 / 529)
+    return score >= (gx.ff_members ? 3.0e5 : 1.5e5);
+}
+bool ff_wanted(const vp_ctx* c, const LaunchPlan& p, size_t i) {
+    const Instrument& x = c->inst[i];
+    if (!x.ff_on || !c->d_ff || c->tune.farfield == 0) return false;
+    if (c->tune.farfield > 0) return true;
+    const vp::InstDev& gx = geom_of(x, p.sel);
+    double score = ff_score(x, gx, p.Wp);
+    if (!c->tune.no_shared_prep && !c->profiling) {
+        size_t r0 = i;
+        while (r0 > 0 && c->inst[r0].same_lines_as_prev) --r0;
+        const size_t partner = r0 + ((i - r0) ^ 1);
+        const bool in_run = partner < c->inst.size() && (partner < i ? true : c->inst[partner].same_lines_as_prev) &&
+                            (partner > i || c->inst[i].same_lines_as_prev);
+        if (in_run && geom_of(c->inst[partner], p.sel).ff_members == gx.ff_members)
+            score += ff_score(c->inst[partner], geom_of(c->inst[partner], p.sel), p.Wp);
+    }
+    return ff_pays(gx, score);
+}
+// the next instrument's too, in the same launch, when it has these line tables (the same records)
+bool ff_paired(const vp_ctx* c, const LaunchPlan& p, size_t k) {
+    const Instrument* nx = (k + 1 < c->inst.size() && !c->profiling) ? &c->inst[k + 1] : nullptr;
+    return nx && nx->same_lines_as_prev && !c->tune.no_shared_prep && ff_wanted(c, p, k + 1) &&
+           geom_of(*nx, p.sel).ff_members == geom_of(c->inst[k], p.sel).ff_members;
+}
+// the tile offsets and weights the finalize launch takes by value (n_inst = 0: more instruments than it holds -- the launch reads them from memory)
+vp::FinalizeByValue finalize_by_value(const vp_ctx* c, const LaunchPlan& p) {
+    vp::FinalizeByValue bv{};
+    const size_t ni = c->inst.size();
+    if (ni > (size_t)vp::FIN_MAX_INST) return bv;
+    bv.n_inst = (int)ni;
+    int off = 0;
+    for (size_t k = 0; k < ni; ++k) {
+        bv.tile_off[k] = off;
+        off += geom_of(c->inst[k], p.sel).ntiles;
+        bv.sum_logw[k] = c->inst[k].sum_logw;
+    }
+    bv.tile_off[ni] = off;
+    return bv;
+}
+// plan kind 3: one record-preparation launch, all instruments' tiles in one launch, the final reduction
+void enqueue_tile_multi(vp_ctx* c, const LaunchPlan& p, int W, const double* d_theta, double* d_out, const vp::FinalizeArgs& fin, hipStream_t s) {
+    const size_t ni = c->inst.size();
+    const Instrument& in0 = c->inst[0];
+    launch_prep(c, in0, d_theta, W, 1, d_out, GenFlags{}, s);
+    vp::InstDev dk[4] = {in0.dev_w, in0.dev_w, in0.dev_w, in0.dev_w};
+    vp::TileMulti tb{};
+    int tsum = 0;
+    for (size_t k = 0; k < ni; ++k) {
+        dk[k] = c->inst[k].dev_w;
+        tb.off[k] = tsum;
+        if (k > 0) tb.t[k - 1] = tsum;
+        tsum += dk[k].ntiles;
+    }
+    for (size_t k = ni; k < 4; ++k) { tb.t[k - 1] = tsum; tb.off[k] = tsum; }
+    const int nt = fin.total_tiles;
+    hipLaunchKernelGGL((in0.dev.method == VP_VOIGT_FAST ? vp::tile_kernel_multi<1> : vp::tile_kernel_multi<0>), dim3(W, nt), dim3(64), walker_wave_lds(c), s,
+                       dk[0], dk[1], dk[2], dk[3], tb, (int)ni, c->d_lc, c->d_flags, c->d_partial, nt, fin);
+    if (!p.fmode)        // (two to four instruments: always by value)
+        hipLaunchKernelGGL((vp::finalize_kernel<true>), dim3((W + 63) / 64), dim3(64), 0, s, c->d_partial, nt, W, c->d_flags, fin, finalize_by_value(c, p),
+                           c->gather_rep ? *c->gather_rep : vp::Replicas{});
+}
+// the blocks' far-field expansions of instrument k from the records just made, into ff; paired: and behind them, in the same launch,
+// those of instrument k + 1
+void launch_farfield(const vp_ctx* c, const LaunchPlan& p, size_t k, double* ff, bool paired, int W, hipStream_t s) {
+    const Instrument& in = c->inst[k];
+    vp::InstDev g2 = geom_of(in, p.sel), g3 = geom_of(c->inst[paired ? k + 1 : k], p.sel);
+    const int nbk = g2.ntiles * g2.ff_nblk, nbx0 = (nbk + 63) / 64, nbx1 = (g3.ntiles * g3.ff_nblk + 63) / 64;
+    g2.ff = ff;
+    g3.ff = ff + (size_t)W * nbk * vp::FF_STRIDE;
+    const size_t ffl = vp::farfield_lds_bytes(in.lines.L, in.lines.NCm);
+    const dim3 block(64 * vp::FF_WAVES);
+    if (paired)
+        hipLaunchKernelGGL((g2.ff_members ? vp::farfield_kernel2<9, true> : vp::farfield_kernel2<6, false>), dim3(nbx0 + nbx1, W), block, ffl, s, g2, g3, nbx0,
+                           in.lines, c->d_lc, W);
+    else
+        hipLaunchKernelGGL((g2.ff_members ? vp::farfield_kernel<9, true> : vp::farfield_kernel<6, false>), dim3(nbx0, W), block, ffl, s, g2, in.lines, c->d_lc, W);
+}
+// Which launches a batch gets, for Wp rows (a block of a larger batch that other contexts share is planned for the whole batch's rows:
+// same structure, hence the same bits, as the whole batch on one context).  Reads the context, writes nothing.
+LaunchPlan plan_lnprob(vp_ctx* c, int Wp) {
+    LaunchPlan p;
+    p.Wp = Wp;
+    if (walker_applies(c, Wp)) {
+        p.kind = 1;
+        p.split = walker_split_for(c, Wp);
+        return p;
+    }
+    // Geometry: a batch whose full-size tiles would leave most wave slots empty is cut into one-pass
+    // tiles instead (twice the workgroups, half the per-wave latency): measured better up to 384
+    // walkers x 12 tiles (30.2 vs 31.1 us), equal at 448, worse at 512 (256 CUs x 4 SIMDs x 6 waves =
+    // 6144 slots).
+    p.sel = ((long)Wp * c->total_tiles_g[0] <= 4800) ? 1 : 0;
+    if (c->tune.geom >= 0) p.sel = c->tune.geom ? 1 : 0;
+    // Final reduction (bit-identical either way, see tile_kernel): fused into the tile kernel -- the
+    // last-arriving tile of a walker, by ticket -- while the batch leaves wave slots empty; a small launch of
+    // its own (one lane per walker) once the batch fills them, where the ticket's L2 round trips at the end of
+    // every tile wave cost more than a launch.  Measured on C1 (us per pass, own launch / ticket): 256
+    // walkers 26.5 / 26.7, 512: 32.3 / 33.0-33.9, 2048: 88.9 / 92.5, 8192: 314 / 329.
+    p.fmode = ((long)Wp * c->total_tiles_g[0] < 6144) ? 1 : 0;
+    if (tile_multi_applies(c, Wp)) {
+        p.kind = 3;
+        p.sel = 2;
+        // (final reduction by its own launch: with these many single-wave tiles per walker the ticket's round trips at the
+        //  end of every wave cost more -- C3 at 64 walkers 56.9 us by ticket, 47.6 by launch; scripts/structure_check.py)
+        p.fmode = 0;
+    }
+    if (c->tune.finalize >= 0) p.fmode = c->tune.finalize ? 1 : 0;      // 0: own launch, 1: ticket
+    if (c->gather_rep) p.fmode = 0;                  // (the finalize launch is what writes into the ranks' gathered vectors)
+    // every instrument's expansions have their own stretch of the workspace (W x its blocks), in instrument order
+    for (size_t k = 0, blk = 0; p.kind == 0 && k < c->inst.size(); ++k) {
+        const vp::InstDev& gk = geom_of(c->inst[k], p.sel);
+        if (ff_wanted(c, p, k)) { p.kind = 2; p.ff_first = (int)k; p.ff_first_blk = (int)blk; }
+        if (c->inst[k].ff_on) blk += (size_t)gk.ntiles * gk.ff_nblk;
+    }
+    return p;
+}
+// what vp_last_launch_kind, vp_last_walker_split and vp_last_farfield_info report of a batch of W rows launched by plan p
+void record_launch(vp_ctx* c, const LaunchPlan& p, int W) {
+    if (p.kind >= 0) { c->last_kind = p.kind; c->last_split = p.split; }
+    c->last_ff = vp_ctx::LastFF{};
+    if (p.ff_first < 0) return;
+    const vp::InstDev& g = geom_of(c->inst[p.ff_first], p.sel);
+    c->last_ff = vp_ctx::LastFF{c->d_ff + (size_t)W * p.ff_first_blk * vp::FF_STRIDE, W, g.ntiles * g.ff_nblk, g.ff_members, p.ff_first};
+}
+// enqueue the launches of plan p for W rows of device-resident theta / out
+int enqueue_plan(vp_ctx* c, const LaunchPlan& p, int W, const double* d_theta, double* d_out, hipStream_t s) {
     const bool prof = c->profiling;
     size_t m0 = prof ? prof_mark(c, s) : 0;
-    c->last_kind = 0;
-    c->last_ff = vp_ctx::LastFF{};
-    const int Wp = c->policy_W > 0 ? c->policy_W : W;       // rows the launch structure is chosen for
-    if (walker_applies(c, Wp)) {
-        c->last_kind = 1;
-        launch_walker(c, W, d_theta, d_out, s, c->gather_rep);
+    if (p.kind == 1) {
+        launch_walker(c, p, W, d_theta, d_out, s);
         if (prof) {
             size_t m1 = prof_mark(c, s);
             c->spans.push_back({m0, m1, 1});
@@ -372,165 +538,39 @@ int enqueue_lnprob(vp_ctx* c, int W, const double* d_theta, double* d_out, hipSt
         HIP_TRY(c, hipGetLastError());
         return VP_OK;
     }
-    // Geometry: a batch whose full-size tiles would leave most wave slots empty is cut into one-pass
-    // tiles instead (twice the workgroups, half the per-wave latency): measured better up to 384
-    // walkers x 12 tiles (30.2 vs 31.1 us), equal at 448, worse at 512 (256 CUs x 4 SIMDs x 6 waves =
-    // 6144 slots).
-    int sel = ((long)Wp * c->total_tiles_g[0] <= 4800) ? 1 : 0;
-    if (c->tune.geom >= 0) sel = c->tune.geom ? 1 : 0;
-    const int ntot = c->total_tiles_g[sel];
-    // Final reduction (bit-identical either way, see tile_kernel): fused into the tile kernel -- the
-    // last-arriving tile of a walker, by ticket -- while the batch leaves wave slots empty; a small launch of
-    // its own (one lane per walker) once the batch fills them, where the ticket's L2 round trips at the end of
-    // every tile wave cost more than a launch.  Measured on C1 (us per pass, own launch / ticket): 256
-    // walkers 26.5 / 26.7, 512: 32.3 / 33.0-33.9, 2048: 88.9 / 92.5, 8192: 314 / 329.
-    int fmode = ((long)Wp * c->total_tiles_g[0] < 6144) ? 1 : 0;
-    if (c->tune.finalize >= 0) fmode = c->tune.finalize ? 1 : 0;      // 0: own launch, 1: ticket
-    if (c->gather_rep) fmode = 0;                    // (the finalize launch is what writes into the ranks' gathered vectors)
-    const bool fused = fmode != 0;
-    const vp::Replicas frep = c->gather_rep ? *c->gather_rep : vp::Replicas{};
-    const vp::FinalizeArgs fin{c->d_ticket, c->d_tile_off + sel * (c->inst.size() + 1), c->d_sum_logw,
-                               d_out, (int)c->inst.size(), ntot, fmode};
-    // ---- several instruments with one set of records, small batch: all their tiles in ONE launch (tile_kernel_multi)
-    {
-        const size_t ni = c->inst.size();
-        bool multi = !prof && ni >= 2 && ni <= 4 && c->tune.tile_multi != 0 && !c->tune.no_shared_prep;
-        size_t lds = 0;
-        long waves = 0;
-        for (size_t k = 0; multi && k < ni; ++k) {
-            const Instrument& in = c->inst[k];
-            if (k > 0 && !in.same_lines_as_prev) multi = false;
-            if (in.lds_w == 0 || in.dev.method != c->inst[0].dev.method || in.nanfix) multi = false;
-            if (in.needs_generic && in.dev.method == VP_VOIGT_WOFZ) multi = false;
-            lds = std::max(lds, in.lds_w);
-            waves += (long)Wp * in.dev_w.ntiles;
-        }
-        // (measured on C3, two instruments of 8192 pixels = 52 single-wave tiles per walker, us per pass, launches / one launch:
-        //  64 walkers 67.5 / 47.6, 256: 89.2 / 92.5, 512: 143.1 / 143.9, 1024: 229 / 251, 2048: 401 / 468 -- the long LSF's tiles carry
-        //  more halo as single waves, which only a batch that leaves the GPU mostly idle does not feel)
-        if (multi && c->tune.tile_multi < 0 && waves > 6144) multi = false;
-        if (multi) {
-            c->last_kind = 3;
-            const Instrument& in0 = c->inst[0];
-            if (prof) (void)0;
-            launch_prep(c, in0, d_theta, W, 1, d_out, (int*)nullptr, s);
-            vp::InstDev dk[4] = {in0.dev_w, in0.dev_w, in0.dev_w, in0.dev_w};
-            vp::TileMulti tb{};
-            int tsum = 0;
-            for (size_t k = 0; k < ni; ++k) {
-                dk[k] = c->inst[k].dev_w;
-                tb.off[k] = tsum;
-                if (k > 0) tb.t[k - 1] = tsum;
-                tsum += dk[k].ntiles;
-            }
-            for (size_t k = ni; k < 4; ++k) { tb.t[k - 1] = tsum; tb.off[k] = tsum; }
-            const int nt = c->total_tiles_w;
-            // (final reduction by its own launch: with these many single-wave tiles per walker the ticket's round trips at the
-            //  end of every wave cost more -- C3 at 64 walkers 56.9 us by ticket, 47.6 by launch; scripts/structure_check.py)
-            int fm = 0;
-            if (c->tune.finalize >= 0) fm = c->tune.finalize ? 1 : 0;
-            if (c->gather_rep) fm = 0;
-            const vp::FinalizeArgs fw{c->d_ticket, c->d_tile_off + 2 * (ni + 1), c->d_sum_logw, d_out, (int)ni, nt, fm};
-            const dim3 grid(W, nt), block(64);
-            if (in0.dev.method == VP_VOIGT_FAST)
-                hipLaunchKernelGGL((vp::tile_kernel_multi<1>), grid, block, lds, s, dk[0], dk[1], dk[2], dk[3], tb, (int)ni, c->d_lc, c->d_flags, c->d_partial, nt, fw);
-            else
-                hipLaunchKernelGGL((vp::tile_kernel_multi<0>), grid, block, lds, s, dk[0], dk[1], dk[2], dk[3], tb, (int)ni, c->d_lc, c->d_flags, c->d_partial, nt, fw);
-            if (!fm) {
-                vp::FinalizeByValue bv{};
-                bv.n_inst = (int)ni;
-                for (size_t k = 0; k < ni; ++k) { bv.tile_off[k] = tb.off[k]; bv.sum_logw[k] = c->inst[k].sum_logw; }
-                bv.tile_off[ni] = nt;
-                hipLaunchKernelGGL((vp::finalize_kernel<true>), dim3((W + 63) / 64), dim3(64), 0, s, c->d_partial, nt, W, c->d_flags, fw, bv, frep);
-            }
-            HIP_TRY(c, hipGetLastError());
-            return VP_OK;
-        }
+    const size_t ni = c->inst.size();
+    const int ntot = p.sel == 2 ? c->total_tiles_w : c->total_tiles_g[p.sel];
+    const vp::FinalizeArgs fin{c->d_ticket, c->d_tile_off + p.sel * (ni + 1), c->d_sum_logw, d_out, (int)ni, ntot, p.fmode};
+    if (p.kind == 3) {
+        enqueue_tile_multi(c, p, W, d_theta, d_out, fin, s);
+        HIP_TRY(c, hipGetLastError());
+        return VP_OK;
     }
+    int tile_off = 0;
+    size_t ff_blk = 0;                               // blocks per row the expansions of the instruments so far have in the workspace
     bool ff_made = false;                            // this instrument's expansions came with the previous one's launch
     GenFlags gf{c->d_genflag, nullptr, nullptr, nullptr, 0};     // (the flags of the records in the workspace: shared by instruments that share those)
     int rc_gf = VP_OK;
-    for (size_t k = 0; k < c->inst.size(); ++k) {
+    for (size_t k = 0; k < ni; ++k) {
         const Instrument& in = c->inst[k];
         const bool gen = in.needs_generic && in.dev.method == VP_VOIGT_WOFZ;
         if (!(k > 0 && in.same_lines_as_prev && !c->tune.no_shared_prep)) {       // (same line tables as the previous instrument: its records and
                                                        // generic-path flags are still in the workspace)
             if (gen && (rc_gf = genflag_acquire(c, W, s, &gf))) return rc_gf;
-            launch_prep(c, in, d_theta, W, k == 0 ? 1 : 0, d_out, gen ? gf.use : (int*)nullptr, s, gen ? gf.clear : (int*)nullptr,
-                        gen ? gf.any : (int*)nullptr, gen ? gf.any_clear : (int*)nullptr);
+            launch_prep(c, in, d_theta, W, k == 0 ? 1 : 0, d_out, gen ? gf : GenFlags{}, s);
         }
-        const vp::InstDev& geom = sel ? in.dev_s : in.dev;
-        // (the extra launch costs ~20 us; what it saves grows with walkers x blocks x lines -- measured on C2, us per pass
-        // without / with: 128 walkers 54.8 / 60.5, 256 (0.42e6): 72.7 / 71.5, 512: 111.8 / 98.3, 1024: 188.8 / 153.1,
-        // 2048: 349.0 / 260.5.  Below that the lines are walked directly unless "farfield" = 1 asks for the expansions.
-        // What the expansions save is one evaluation per pass for every ITEM they cover (a multipole cluster or a line
-        // outside clusters: C2 has 9, a 40-line FeII fit of 8 clusters 8, one of 20 lines 4), ff_cover of them (estimated
-        // when the instrument is added); the crossover sits near 2e5 covered (walker, block, item) triples: C2 at 256
-        // walkers (0.195e6) 72.7 / 71.5 us, the 40-line FeII fit at 1024 walkers (0.17e6) 164.9 / 161.1, the 20-line one
-        // at 1024 (0.09e6) 90.4 / 93.2.
-        // (round 3, after the launch itself got cheaper -- records staged in LDS, faster record preparation in front of it --: on
-        //  from 1.5e5 covered triples: C2 at 256 walkers (1.95e5) 57.2 / 54.9, C4 at 64 (0.9e5) 119.5 / 130.8.)
-        // (instruments that share their records come in pairs whose expansions are ONE launch: the pair's triples count together
-        //  -- C3, us per pass without / with: 128 walkers 66.4 / 70.3, 256: 68.5 / 67.0, 512: 103.8 / 94.4)
-        auto ff_score = [&](size_t i) {
-            const Instrument& x = c->inst[i];
-            const vp::InstDev& gx = sel ? x.dev_s : x.dev;
-            return x.ff_on ? x.ff_cover * (double)Wp * gx.ntiles * gx.ff_nblk * x.ff_items : 0.0;
-        };
-        auto ff_wanted = [&](size_t i) {
-            const Instrument& x = c->inst[i];
-            if (!x.ff_on || !c->d_ff || c->tune.farfield == 0) return false;
-            if (c->tune.farfield > 0) return true;
-            double score = ff_score(i);
-            if (!c->tune.no_shared_prep && !prof) {
-                size_t r0 = i;
-                while (r0 > 0 && c->inst[r0].same_lines_as_prev) --r0;
-                const size_t partner = r0 + ((i - r0) ^ 1);
-                const bool in_run = partner < c->inst.size() && (partner < i ? true : c->inst[partner].same_lines_as_prev) &&
-                                    (partner > i || c->inst[i].same_lines_as_prev);
-                if (in_run && (sel ? c->inst[partner].dev_s : c->inst[partner].dev).ff_members == (sel ? x.dev_s : x.dev).ff_members)
-                    score += ff_score(partner);
-            }
-            // (instruments whose cluster members enter the expansions line by line pay more for the launch: C4 at 64 walkers
-            //  -- 1.8e5 -- 119.5 / 130.3 us, at 512 walkers 636 / 529)
-            return score >= ((sel ? x.dev_s : x.dev).ff_members ? 3.0e5 : 1.5e5);
-        };
-        // every instrument's expansions have their own stretch of the workspace (W x its blocks), in instrument order
-        size_t ff_off = 0;
-        for (size_t i = 0; i < k; ++i) {
-            const vp::InstDev& gi = sel ? c->inst[i].dev_s : c->inst[i].dev;
-            if (c->inst[i].ff_on) ff_off += (size_t)W * gi.ntiles * gi.ff_nblk * vp::FF_STRIDE;
-        }
-        double* ff = ff_wanted(k) ? c->d_ff + ff_off : nullptr;
-        if (ff && !ff_made) {                            // the blocks' far-field expansions from the records just made
-            c->last_kind = 2;
-            vp::InstDev g2 = geom;
-            g2.ff = ff;
-            const int nbk = geom.ntiles * geom.ff_nblk;
-            if (c->last_ff.inst < 0) c->last_ff = vp_ctx::LastFF{ff, W, nbk, g2.ff_members, (int)k};
-            const size_t ffl = vp::farfield_lds_bytes(in.lines.L, in.lines.NCm);
-            // the next instrument's too, in the same launch, when it has these line tables (the same records)
-            const Instrument* nx = (k + 1 < c->inst.size() && !prof) ? &c->inst[k + 1] : nullptr;
-            if (nx && nx->same_lines_as_prev && !c->tune.no_shared_prep && ff_wanted(k + 1) && (sel ? nx->dev_s : nx->dev).ff_members == g2.ff_members) {
-                vp::InstDev g3 = sel ? nx->dev_s : nx->dev;
-                g3.ff = ff + (size_t)W * nbk * vp::FF_STRIDE;
-                const int nbk1 = g3.ntiles * g3.ff_nblk, nbx0 = (nbk + 63) / 64, nbx1 = (nbk1 + 63) / 64;
-                if (g2.ff_members) hipLaunchKernelGGL((vp::farfield_kernel2<9, true>), dim3(nbx0 + nbx1, W), dim3(64 * vp::FF_WAVES), ffl, s, g2, g3, nbx0, in.lines, c->d_lc, W);
-                else hipLaunchKernelGGL((vp::farfield_kernel2<6, false>), dim3(nbx0 + nbx1, W), dim3(64 * vp::FF_WAVES), ffl, s, g2, g3, nbx0, in.lines, c->d_lc, W);
-                ff_made = true;                          // (consumed by the next instrument's pass of this loop)
-            } else {
-                if (g2.ff_members) hipLaunchKernelGGL((vp::farfield_kernel<9, true>), dim3((nbk + 63) / 64, W), dim3(64 * vp::FF_WAVES), ffl, s, g2, in.lines, c->d_lc, W);
-                else hipLaunchKernelGGL((vp::farfield_kernel<6, false>), dim3((nbk + 63) / 64, W), dim3(64 * vp::FF_WAVES), ffl, s, g2, in.lines, c->d_lc, W);
-            }
-        } else if (ff) {
-            c->last_kind = 2;
-            ff_made = false;
-        }
+        const vp::InstDev& geom = geom_of(in, p.sel);
+        TileOpts o;
+        o.geom = &geom;
+        o.ff = ff_wanted(c, p, k) ? c->d_ff + (size_t)W * ff_blk * vp::FF_STRIDE : nullptr;
+        o.gen_slots = gf.slots;
+        if (in.ff_on) ff_blk += (size_t)geom.ntiles * geom.ff_nblk;
+        const bool ff_launch = o.ff && !ff_made;
+        ff_made = ff_launch && ff_paired(c, p, k);       // (consumed by the next instrument's pass of this loop)
+        if (ff_launch) launch_farfield(c, p, k, o.ff, ff_made, W, s);
         size_t m1 = prof ? prof_mark(c, s) : 0;
-        launch_tile<0, false>(in, c->d_lc, c->d_flags, c->d_partial, ntot, tile_off, W, s, fin,
-                              gen ? gf.use : (const int*)nullptr, &geom, 1, ff);
-        if (gen)
-            launch_tile<0, true>(in, c->d_lc, c->d_flags, c->d_partial, ntot, tile_off, W, s, fin, gf.use, &geom, 1, nullptr, gf.slots);
+        launch_tile<0, false>(in, c->d_lc, c->d_flags, c->d_partial, ntot, tile_off, W, s, fin, gen ? gf.use : (const int*)nullptr, o);
+        if (gen) launch_tile<0, true>(in, c->d_lc, c->d_flags, c->d_partial, ntot, tile_off, W, s, fin, gf.use, o);
         if (prof) {
             size_t m2 = prof_mark(c, s);
             c->spans.push_back({m0, m1, 0});
@@ -539,22 +579,10 @@ int enqueue_lnprob(vp_ctx* c, int W, const double* d_theta, double* d_out, hipSt
         }
         tile_off += geom.ntiles;
     }
-    if (!fused) {
-        vp::FinalizeByValue bv{};
-        const size_t ni = c->inst.size();
-        if (ni <= (size_t)vp::FIN_MAX_INST) {
-            bv.n_inst = (int)ni;
-            int off = 0;
-            for (size_t k = 0; k < ni; ++k) {
-                bv.tile_off[k] = off;
-                off += (sel ? c->inst[k].dev_s : c->inst[k].dev).ntiles;
-                bv.sum_logw[k] = c->inst[k].sum_logw;
-            }
-            bv.tile_off[ni] = off;
-            hipLaunchKernelGGL((vp::finalize_kernel<true>), dim3((W + 63) / 64), dim3(64), 0, s, c->d_partial, ntot, W, c->d_flags, fin, bv, frep);
-        } else {
-            hipLaunchKernelGGL((vp::finalize_kernel<false>), dim3((W + 63) / 64), dim3(64), 0, s, c->d_partial, ntot, W, c->d_flags, fin, bv, frep);
-        }
+    if (!p.fmode) {
+        const vp::FinalizeByValue bv = finalize_by_value(c, p);
+        hipLaunchKernelGGL((bv.n_inst ? vp::finalize_kernel<true> : vp::finalize_kernel<false>), dim3((W + 63) / 64), dim3(64), 0, s, c->d_partial, ntot, W,
+                           c->d_flags, fin, bv, c->gather_rep ? *c->gather_rep : vp::Replicas{});
         if (prof) {
             size_t m3 = prof_mark(c, s);
             c->spans.push_back({m0, m3, 2});
@@ -564,3 +592,12 @@ int enqueue_lnprob(vp_ctx* c, int W, const double* d_theta, double* d_out, hipSt
     return VP_OK;
 }
 
+// enqueue the whole lnprob pipeline for device-resident theta / out: per instrument a prep launch
+// (line records; the first one also applies the box prior and writes -inf rows) and a tile launch;
+// the last-arriving tile workgroup of each walker performs the final reduction.
+// Wp > 0: the rows the launch structure is chosen for, where they are not the batch's own (LaunchPlan::Wp)
+int enqueue_lnprob(vp_ctx* c, int W, const double* d_theta, double* d_out, hipStream_t s, int Wp = 0) {
+    const LaunchPlan p = plan_lnprob(c, Wp > 0 ? Wp : W);
+    record_launch(c, p, W);
+    return enqueue_plan(c, p, W, d_theta, d_out, s);
+}

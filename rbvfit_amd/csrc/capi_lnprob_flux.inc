@@ -54,8 +54,7 @@ static int lnprob_host_begin(vp_ctx* c, int W, int D, const double* theta, int a
             c->arm.seq_inflight = c->arm.seq;
             ++c->arm.used;
             if (++c->arm.used_streak >= 16) c->arm.cooldown_next = 8;
-            c->last_kind = 1;
-            c->last_ff = vp_ctx::LastFF{};
+            record_launch(c, plan_lnprob(c, W), W);       // (a walker launch: prearm_eligible)
         } else {
             c->arm.cur = c->stream;
             if ((rc = enqueue_lnprob(c, W, dp, dp + (size_t)W * D, c->stream))) return rc;
@@ -229,19 +228,20 @@ static int enqueue_model_flux(vp_ctx* c, int inst, int W, const double* d_theta,
     const vp::FinalizeArgs nofin{};
     const int* gf = gfl.use;
     // far lines from the blocks' expansions, as in the lnprob launches (convolved flux; same rule for when the extra launch pays)
-    double* ff = nullptr;
-    c->last_ff = vp_ctx::LastFF{};
-    if (convolved && in.ff_on && c->d_ff && c->tune.flux_farfield != 0) {
-        const double score = in.ff_cover * (double)W * in.dev.ntiles * in.dev.ff_nblk * in.ff_items;
-        if (c->tune.flux_farfield > 0 || score >= (in.dev.ff_members ? 3.0e5 : 1.5e5)) ff = c->d_ff;
-    }
+    LaunchPlan p;
+    p.kind = -1;
+    if (convolved && in.ff_on && c->d_ff && c->tune.flux_farfield != 0 &&
+        (c->tune.flux_farfield > 0 || ff_pays(in.dev, ff_score(in, in.dev, W)))) p.ff_first = inst;
+    record_launch(c, p, W);
+    TileOpts o;
+    o.ff = p.ff_first < 0 ? nullptr : c->d_ff;
+    o.gen_slots = gfl.slots;
     // Batches the walker kernel takes as lnprob batches (one instrument, no cluster records, the workgroups fit the CUs): the rows in
     // ONE launch, workgroup = walker -- records formed in the workgroup, no record-preparation launch in front (C1 at 512 rows
     // 28 -> 24 us); walkers with a line outside the fast domain are left to the generic launch behind it, as in the tile path.
-    if (convolved && !ff && inst == 0 && c->inst.size() == 1 && in.dev.NCm == 0 && c->tune.flux_walker != 0 && !c->profiling &&
+    if (convolved && !o.ff && inst == 0 && c->inst.size() == 1 && in.dev.NCm == 0 && c->tune.flux_walker != 0 && !c->profiling &&
         !c->gather_rep && walker_applies(c, W) && in.dev.method == VP_VOIGT_WOFZ) {
-        vp::WalkerArgs a{d_theta, c->d_lb, c->d_ub, c->d_lc, d_out, 0.0, c->D, (int)(walker_wave_lds(c) / sizeof(double)),
-                         walker_prio_for(c, W), walker_perm_for(c, W)};
+        vp::WalkerArgs a = walker_args(c, W, d_theta, d_out, 0.0);
         a.flux_stride = in.dev.P;
         a.genflag = gfl.use; a.genflag_clear = gfl.clear; a.gen_any = gfl.any; a.gen_any_clear = gfl.any_clear;
         vp::InstDev d0 = in.dev_w;
@@ -249,26 +249,20 @@ static int enqueue_model_flux(vp_ctx* c, int inst, int W, const double* d_theta,
         d0.NCm = 0; t0.NCm = 0;
         hipLaunchKernelGGL((vp::walker_kernel<0, false, false, false, 1>), dim3(W), dim3(64 * walker_tiles(c)), walker_lds_bytes(c), s, d0, t0, a,
                            vp::StretchArgs{});
-        launch_tile<1, true>(in, c->d_lc, nullptr, d_out, in.dev.P, 0, W, s, nofin, gf, nullptr, 1, nullptr, gfl.slots, d_theta, c->D);
+        o.theta_rebuild = d_theta;
+        o.D = c->D;
+        launch_tile<1, true>(in, c->d_lc, nullptr, d_out, in.dev.P, 0, W, s, nofin, gf, o);
         HIP_TRY(c, hipGetLastError());
         return VP_OK;
     }
-    launch_prep(c, in, d_theta, W, 0, nullptr, gfl.use, s, gfl.clear, gfl.any, gfl.any_clear);
-    if (ff) {
-        vp::InstDev g2 = in.dev;
-        g2.ff = ff;
-        const int nbk = g2.ntiles * g2.ff_nblk;
-        c->last_ff = vp_ctx::LastFF{ff, W, nbk, g2.ff_members, inst};
-        const size_t ffl = vp::farfield_lds_bytes(in.lines.L, in.lines.NCm);
-        if (g2.ff_members) hipLaunchKernelGGL((vp::farfield_kernel<9, true>), dim3((nbk + 63) / 64, W), dim3(64 * vp::FF_WAVES), ffl, s, g2, in.lines, c->d_lc, W);
-        else hipLaunchKernelGGL((vp::farfield_kernel<6, false>), dim3((nbk + 63) / 64, W), dim3(64 * vp::FF_WAVES), ffl, s, g2, in.lines, c->d_lc, W);
-    }
+    launch_prep(c, in, d_theta, W, 0, nullptr, gfl, s);
+    if (o.ff) launch_farfield(c, p, inst, o.ff, false, W, s);
     if (convolved) {
-        launch_tile<1, false>(in, c->d_lc, nullptr, d_out, in.dev.P, 0, W, s, nofin, gf, nullptr, 1, ff);
-        if (gen) launch_tile<1, true>(in, c->d_lc, nullptr, d_out, in.dev.P, 0, W, s, nofin, gf, nullptr, 1, nullptr, gfl.slots);
+        launch_tile<1, false>(in, c->d_lc, nullptr, d_out, in.dev.P, 0, W, s, nofin, gf, o);
+        if (gen) launch_tile<1, true>(in, c->d_lc, nullptr, d_out, in.dev.P, 0, W, s, nofin, gf, o);
     } else {
-        launch_tile<2, false>(in, c->d_lc, nullptr, d_out, in.dev.P, 0, W, s, nofin, gf);
-        if (gen) launch_tile<2, true>(in, c->d_lc, nullptr, d_out, in.dev.P, 0, W, s, nofin, gf, nullptr, 1, nullptr, gfl.slots);
+        launch_tile<2, false>(in, c->d_lc, nullptr, d_out, in.dev.P, 0, W, s, nofin, gf, o);
+        if (gen) launch_tile<2, true>(in, c->d_lc, nullptr, d_out, in.dev.P, 0, W, s, nofin, gf, o);
     }
     HIP_TRY(c, hipGetLastError());
     return VP_OK;
@@ -370,15 +364,17 @@ int vp_model_flux_components(vp_ctx* c, int inst, int W, int D, const double* th
     const bool gen = in.dev.method == VP_VOIGT_WOFZ;
     GenFlags gfl{nullptr, nullptr, nullptr, nullptr, 0};
     if (gen && (rc = genflag_acquire(c, W, s, &gfl))) return rc;
-    launch_prep(c, in, c->d_theta, W, 0, nullptr, gfl.use, s, gfl.clear, gfl.any, gfl.any_clear);
+    launch_prep(c, in, c->d_theta, W, 0, nullptr, gfl, s);
     const vp::FinalizeArgs nofin{};
     const size_t nrec = (size_t)(in.dev.L + in.dev.NCm) * vp::LC_STRIDE;
+    TileOpts o;
+    o.grid_z = (int)L;
+    o.gen_slots = gfl.slots;
     for (int w0 = 0; w0 < W; w0 += wblock) {
         const int nw = std::min(wblock, W - w0);
         const int* gf = gen ? gfl.use + w0 : (const int*)nullptr;
-        launch_tile<2, false>(in, c->d_lc + (size_t)w0 * nrec, nullptr, c->d_scratch, (int)(L * P), 0, nw, s, nofin, gf, nullptr, (int)L);
-        if (gen) launch_tile<2, true>(in, c->d_lc + (size_t)w0 * nrec, nullptr, c->d_scratch, (int)(L * P), 0, nw, s, nofin, gf, nullptr, (int)L,
-                                      nullptr, gfl.slots);
+        launch_tile<2, false>(in, c->d_lc + (size_t)w0 * nrec, nullptr, c->d_scratch, (int)(L * P), 0, nw, s, nofin, gf, o);
+        if (gen) launch_tile<2, true>(in, c->d_lc + (size_t)w0 * nrec, nullptr, c->d_scratch, (int)(L * P), 0, nw, s, nofin, gf, o);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipMemcpyAsync(out + (size_t)w0 * L * P, c->d_scratch, (size_t)nw * per_walker, hipMemcpyDeviceToHost, s));
     }

@@ -169,7 +169,7 @@ static int multi_barrier(vp_multi* m) {
 // One ensemble, G device contexts (BASELINE config 4: "2048 zeus walkers sharded over 8 GPUs"; vfit_mcmc.py:425-440,
 // 536-540 fans ONE ensemble over its workers): see csrc/sampler_kernels.h.  Per half-step every context runs its block of
 // the active half -- one walker_kernel launch where vp_stretch_run would use one for the whole half, else propose ->
-// lnprob launches -> accept -- with the launch structure chosen as for the whole half (policy_W), so every row gets
+// lnprob launches -> accept -- with the launch structure chosen as for the whole half (LaunchPlan::Wp), so every row gets
 // the bits a single context gives it; then the event barrier.  Chain: replica 0 keeps it.
 int vp_multi_stretch_run(vp_multi* m, int W, int D, double* pos, double* lnprob, int have_lnprob, int nsteps, double a,
                          uint64_t seed, uint64_t step0, double* chain, double* chain_lnprob, int64_t* naccepted) {
@@ -230,7 +230,6 @@ int vp_multi_stretch_run(vp_multi* m, int W, int D, double* pos, double* lnprob,
         if (have_lnprob) MTRY(hipMemcpyAsync(d.lp, lnprob, (size_t)W * sizeof(double), hipMemcpyHostToDevice, c->stream));
         else {
             // every replica evaluates the whole start state itself (once per run; the same launches as vp_stretch_run's)
-            c->policy_W = 0;
             if ((rc = enqueue_lnprob(c, W, d.pos, d.lp, c->stream))) return multi_fail(m, i, rc);
             hipLaunchKernelGGL(vp::nan_flag_kernel, dim3((W + 255) / 256), dim3(256), 0, c->stream, d.lp, W, d.nan);
         }
@@ -250,7 +249,6 @@ int vp_multi_stretch_run(vp_multi* m, int W, int D, double* pos, double* lnprob,
         MTRY(hipStreamSynchronize(c->stream));
     }
     const int thr = 64;
-    auto finish = [&](int code) { for (int i = 0; i < G; ++i) m->ctx[i]->policy_W = 0; return code; };
     std::vector<double> h_chunk;                       // flags mode: one context's chain chunk on its way to the caller's arrays
     int seq = 0;                                       // half-steps of this call so far
     for (int done = 0; done < nsteps;) {
@@ -264,7 +262,6 @@ int vp_multi_stretch_run(vp_multi* m, int W, int D, double* pos, double* lnprob,
                     vp_ctx* c = m->ctx[i];
                     const int k0 = std::min(i * per, half), nk = std::min(k0 + per, half) - k0;
                     MTRY(hipSetDevice(c->device));
-                    c->policy_W = half;
                     const Dev& d = dv[i];
                     vp::Replicas R{};
                     R.n = G;
@@ -279,26 +276,24 @@ int vp_multi_stretch_run(vp_multi* m, int W, int D, double* pos, double* lnprob,
                                                d.zz, D, s0, k0, 0, seed, step, h, d.nacc, d.nan, cp, cl);
                         continue;
                     }
-                    // (the choice vp_stretch_run makes for the whole half)
-                    const bool one_launch = !c->tune.no_fused_accept && c->tune.walker != 0 && walker_applies(c, half) &&
-                                            (c->inst[0].dev.NCm == 0 || !c->tune.walker_clusters);
-                    if (one_launch) {
+                    const int split = stretch_split(c, half);      // (the choice vp_stretch_run makes for the whole half)
+                    if (split >= 0) {
                         vp::StretchArgs sa{};
                         sa.pos = d.pos; sa.lp = d.lp; sa.nacc = d.nacc; sa.nanflag = d.nan;
                         sa.chain_pos = cp; sa.chain_lp = cl;
                         sa.a = a; sa.seed = seed; sa.step = step; sa.s0 = s0 + k0; sa.c0 = cc0; sa.nC = half; sa.half = h;
                         sa.rep = R;
-                        launch_walker_stretch(c, nk, sa, c->stream, 0, walker_split_for(c, half));    // (the form the WHOLE half would get)
+                        launch_walker_stretch(c, nk, sa, c->stream, 0, split);    // (the form the WHOLE half would get)
                     } else {
                         hipLaunchKernelGGL(vp::stretch_propose_block_kernel, dim3((nk + thr - 1) / thr), dim3(thr), 0, c->stream, d.pos, D, s0,
                                            half, cc0, half, a, seed, step, h, k0, nk, d.prop, d.zz, R);
-                        if ((rc = enqueue_lnprob(c, nk, d.prop, d.lpnew, c->stream))) return finish(multi_fail(m, i, rc));
+                        if ((rc = enqueue_lnprob(c, nk, d.prop, d.lpnew, c->stream, half))) return multi_fail(m, i, rc);
                         hipLaunchKernelGGL(vp::stretch_accept_block_kernel, dim3((nk + thr - 1) / thr), dim3(thr), 0, c->stream, d.pos, d.lp, R,
                                            d.prop, d.lpnew, d.zz, D, s0, k0, nk, seed, step, h, d.nacc, d.nan, cp, cl);
                     }
                     MTRY(hipGetLastError());
                 }
-                if (!flags_mode && (rc = multi_barrier(m))) return finish(multi_fail(m, 0, rc));
+                if (!flags_mode && (rc = multi_barrier(m))) return multi_fail(m, 0, rc);
             }
             if (chain && !flags_mode) {
                 vp_ctx* c = c0; const int i = 0;
@@ -311,7 +306,7 @@ int vp_multi_stretch_run(vp_multi* m, int W, int D, double* pos, double* lnprob,
                 for (int j = 1; j < G; ++j) {
                     vp_ctx* cj = m->ctx[j];
                     if (hipSetDevice(cj->device) != hipSuccess || hipStreamWaitEvent(cj->stream, m->ev[0], 0) != hipSuccess) {
-                        cj->err = "hipStreamWaitEvent failed"; return finish(multi_fail(m, j, VP_EHIP));
+                        cj->err = "hipStreamWaitEvent failed"; return multi_fail(m, j, VP_EHIP);
                     }
                 }
             }
@@ -375,9 +370,9 @@ int vp_multi_stretch_run(vp_multi* m, int W, int D, double* pos, double* lnprob,
         }
     }
 #undef MTRY
-    if (any_timeout) { c0->err = "vp_multi_stretch_run: a context gave up waiting for its peers' half-step (in-kernel flags; try the multi_sync = 0 option)"; return finish(multi_fail(m, 0, VP_ESTATE)); }
-    if (any_nan) { c0->err = "vp_multi_stretch_run: Probability function returned NaN"; return finish(multi_fail(m, 0, VP_ENAN)); }
-    return finish(VP_OK);
+    if (any_timeout) { c0->err = "vp_multi_stretch_run: a context gave up waiting for its peers' half-step (in-kernel flags; try the multi_sync = 0 option)"; return multi_fail(m, 0, VP_ESTATE); }
+    if (any_nan) { c0->err = "vp_multi_stretch_run: Probability function returned NaN"; return multi_fail(m, 0, VP_ENAN); }
+    return VP_OK;
 }
 
 int vp_multi_slice_run(vp_multi* m, int W, int D, double* pos, double* lnprob, int have_lnprob, int nsteps, double* mu,

@@ -39,7 +39,7 @@ void prearm_cancel(vp_ctx* c) {
 }
 // may the NEXT call of this shape be started through a pre-armed launch?
 bool prearm_eligible(vp_ctx* c, int W, size_t theta_bytes) {
-    return c->tune.prearm != 0 && c->arm.bar != 0 && c->tune.host_spin >= 2 && !c->sentinel_unsafe && !c->gather_rep && !c->profiling && c->policy_W == 0 &&
+    return c->tune.prearm != 0 && c->arm.bar != 0 && c->tune.host_spin >= 2 && !c->sentinel_unsafe && !c->gather_rep && !c->profiling &&
            theta_bytes <= (size_t)std::max(0l, c->tune.zerocopy_max) && !c->tune.no_zerocopy && walker_applies(c, W);
 }
 int prearm_launch(vp_ctx* c, int W) {
@@ -83,7 +83,7 @@ int prearm_launch(vp_ctx* c, int W) {
     if (c->arm.seq == 0) c->arm.seq = 1;
     hipStream_t s = c->stream;
     double* dp = c->h_pinned_dev;
-    launch_walker(c, W, dp, dp + (size_t)W * c->D, s, nullptr, true);
+    launch_walker(c, plan_lnprob(c, W), W, dp, dp + (size_t)W * c->D, s, true);
     HIP_TRY(c, hipGetLastError());
     c->arm.live = true;
     c->arm.dirty = true;

@@ -49,11 +49,8 @@ int vp_stretch_run(vp_ctx* c, int W, int D, double* pos, double* lnprob, int hav
         if (h_nan0) return fail(c, VP_ENAN, "vp_stretch_run: the initial lnprob holds NaN (Probability function returned NaN)");
     }
     const int thr = 64;
-    // whole half-step in one launch (proposal, lnprob, accept inside each walker's workgroup) where the walker kernel
-    // applies to a half-ensemble batch and the instrument has no cluster records
-    const bool one_launch = !c->tune.no_fused_accept && c->tune.walker != 0 && walker_applies(c, half) &&
-                            (c->inst[0].dev.NCm == 0 || !c->tune.walker_clusters);
-    const int split = one_launch ? walker_split_for(c, half) : 0;      // a walker of the half-step as several workgroups (WalkerArgs::split)
+    const int split = stretch_split(c, half);
+    const bool one_launch = split >= 0;
     const bool fuse = W <= 1024 && !c->tune.no_fused_accept;   // accept + next proposal in one launch
     const int wthr = ((W + 63) / 64) * 64;
     bool have_prop = false;                                   // is the proposal of the coming pass already enqueued?
@@ -62,14 +59,10 @@ int vp_stretch_run(vp_ctx* c, int W, int D, double* pos, double* lnprob, int hav
     // the one it waits for must never be left without one: two half-ensembles of workgroups within what the CUs hold at once.
     bool ovl = false;
     if (one_launch && c->tune.stretch_overlap != 0 && nsteps > 0) {
-        if (c->num_cus == 0) {
-            int n = 0;
-            if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess) c->num_cus = n;
-        }
         const int nt = split > 0 ? split_shape(c, split).waves : walker_tiles(c);
         const size_t wl = split > 0 ? split_shape(c, split).lds : walker_lds_bytes(c);
         const long per_cu = std::max(1, std::min((split > 0 ? 28 : 24) / std::max(1, nt), (int)(c->lds_limit / wl)));
-        ovl = c->tune.stretch_overlap > 0 || (per_cu >= 2 && 2l * half * std::max(1, split) <= per_cu * (long)c->num_cus);
+        ovl = c->tune.stretch_overlap > 0 || (per_cu >= 2 && 2l * half * std::max(1, split) <= per_cu * (long)ctx_num_cus(c));
         if (ovl && !c->stream2) {
             if (hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) != hipSuccess ||
                 hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
@@ -191,7 +184,7 @@ int vp_stretch_run(vp_ctx* c, int W, int D, double* pos, double* lnprob, int hav
 // (vp_multi_slice_run) every context holds the whole sampler state and runs the SAME control kernels on it -- begin,
 // init, update, tune are deterministic functions of that state -- while each round's lnprob batch of B trial rows is cut
 // into blocks of ceil(B / G) rows, one per context, evaluated with the launch structure the whole batch would get
-// (policy_W), and written into EVERY replica's result vector (one double per row through peer-mapped pointers), followed
+// (LaunchPlan::Wp), and written into EVERY replica's result vector (one double per row through peer-mapped pointers), followed
 // by the event barrier.  The replicas therefore stay identical bit for bit, and equal to the single-context run.
 static int multi_barrier(vp_multi* m);
 namespace { __global__ void scatter_rows_kernel(const double* __restrict__ src, int n, int lo, vp::Replicas R) {
@@ -261,7 +254,6 @@ static int slice_run_impl(vp_multi* m, vp_ctx* const* cx, int G, int W, int D, d
         STRY(i, hipMemcpyAsync(d.mu, h_mu, sizeof(h_mu), hipMemcpyHostToDevice, d.s));
         STRY(i, hipMemsetAsync(d.ll, 0, 4 * sizeof(long long), d.s));
         STRY(i, hipMemsetAsync(d.nact, 0, 16 * sizeof(int), d.s));
-        ci->policy_W = 0;
         if (have_lnprob) STRY(i, hipMemcpyAsync(d.lp, lnprob, (size_t)W * sizeof(double), hipMemcpyHostToDevice, d.s));
         else if ((rc = enqueue_lnprob(ci, W, d.pos, d.lp, d.s))) { *bad = i; return rc; }     // (every replica: once per run)
     }
@@ -293,8 +285,7 @@ static int slice_run_impl(vp_multi* m, vp_ctx* const* cx, int G, int W, int D, d
     }
     int parity = 0;                                  // which of the two row-result vectors the coming round fills (G > 1)
     int tb = 0;                                      // which of the two trial batches the coming round evaluates
-    auto done_ = [&](int code) { for (int i = 0; i < G; ++i) cx[i]->policy_W = 0; return code; };
-    if (G > 1 && (rc = multi_barrier(m))) return done_(rc);
+    if (G > 1 && (rc = multi_barrier(m))) return rc;
     vp::SliceRun P{};
     P.W = W; P.half = half; P.D = D; P.batch_rows = B; P.maxsteps = maxsteps; P.patience = patience;
     P.round_limit = (int)std::min<long long>(4ll * maxsteps + 4096, 1ll << 30);
@@ -328,8 +319,7 @@ static int slice_run_impl(vp_multi* m, vp_ctx* const* cx, int G, int W, int D, d
             } else {
                 const int lo = std::min(i * per, B), n = std::min(lo + per, B) - lo;
                 if (n <= 0) continue;
-                ci->policy_W = B;
-                if ((rc = enqueue_lnprob(ci, n, d.trial + ((size_t)tb * B + lo) * D, d.blk, d.s))) { *bad = i; return rc; }
+                if ((rc = enqueue_lnprob(ci, n, d.trial + ((size_t)tb * B + lo) * D, d.blk, d.s, B))) { *bad = i; return rc; }
                 hipLaunchKernelGGL(scatter_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, d.s, d.blk, n, lo, R);
             }
         }
@@ -372,7 +362,7 @@ static int slice_run_impl(vp_multi* m, vp_ctx* const* cx, int G, int W, int D, d
                         STRY(0, hipSetDevice(c->device));
                         const hipError_t q = hipStreamQuery(dv[0].s);
                         if (q != hipErrorNotReady) {     // the queue ran dry (or failed) without the word moving
-                            if (q != hipSuccess) { (void)hipGetLastError(); *bad = 0; return done_(fail(c, VP_EHIP, std::string("vp_slice_run: ") + hipGetErrorString(q))); }
+                            if (q != hipSuccess) { (void)hipGetLastError(); *bad = 0; return fail(c, VP_EHIP, std::string("vp_slice_run: ") + hipGetErrorString(q)); }
                             if (!__atomic_load_n(const_cast<int*>(h_words + 1), __ATOMIC_ACQUIRE) &&
                                 __atomic_load_n(const_cast<int*>(h_words), __ATOMIC_RELAXED) == seen) h_words = nullptr;   // word not delivered: poll by copy
                         }
@@ -380,11 +370,11 @@ static int slice_run_impl(vp_multi* m, vp_ctx* const* cx, int G, int W, int D, d
                     }
                     continue;
                 }
-                if ((rc = round())) return done_(rc);
+                if ((rc = round())) return rc;
                 ++enq;
             } else {                                 // no mapped word: look at the device's state every few rounds
                 for (int r = 0; r < ahead; ++r)
-                    if ((rc = round())) return done_(rc);
+                    if ((rc = round())) return rc;
                 STRY(0, hipSetDevice(c->device));
                 STRY(0, hipMemcpyAsync(h_prog, dv[0].prog, sizeof(h_prog), hipMemcpyDeviceToHost, dv[0].s));
                 STRY(0, hipStreamSynchronize(dv[0].s));
@@ -398,15 +388,15 @@ static int slice_run_impl(vp_multi* m, vp_ctx* const* cx, int G, int W, int D, d
             STRY(i, hipStreamSynchronize(dv[i].s));
         }
         STRY(0, hipGetLastError());
-        if (h_prog[3] == 1) { *bad = 0; return done_(fail(c, VP_ENAN, "vp_slice_run: Log Probability returned NaN")); }
-        if (h_prog[3]) { *bad = 0; return done_(fail(c, VP_ESTATE, "vp_slice_run: a slice did not terminate")); }
+        if (h_prog[3] == 1) { *bad = 0; return fail(c, VP_ENAN, "vp_slice_run: Log Probability returned NaN"); }
+        if (h_prog[3]) { *bad = 0; return fail(c, VP_ESTATE, "vp_slice_run: a slice did not terminate"); }
         if (chain) {
             STRY(0, hipMemcpyAsync(chain + (size_t)done * W * D, dv[0].chain, (size_t)n * W * D * sizeof(double), hipMemcpyDeviceToHost, dv[0].s));
             STRY(0, hipMemcpyAsync(chain_lnprob + (size_t)done * W, dv[0].chain + seg * (size_t)W * D, (size_t)n * W * sizeof(double),
                                    hipMemcpyDeviceToHost, dv[0].s));
             STRY(0, hipStreamSynchronize(dv[0].s));
         }
-        if (G > 1 && (rc = multi_barrier(m))) return done_(rc);
+        if (G > 1 && (rc = multi_barrier(m))) return rc;
         done += n;
     }
     STRY(0, hipSetDevice(c->device));
@@ -427,7 +417,7 @@ static int slice_run_impl(vp_multi* m, vp_ctx* const* cx, int G, int W, int D, d
     if (n_evals) *n_evals += (int64_t)h_ll[0];
 #undef STRY
 #undef SFAIL
-    return done_(VP_OK);
+    return VP_OK;
 }
 
 int vp_slice_run(vp_ctx* c, int W, int D, double* pos, double* lnprob, int have_lnprob, int nsteps, double* mu,
