@@ -337,6 +337,35 @@ int ensure_scratch(vp_ctx* c, size_t bytes) {
     return VP_OK;
 }
 
+// Bump allocator over a buffer.  An entry point that cuts d_scratch into sub-buffers states its layout ONCE, as a function that
+// fills its Dev struct from an Arena (carve_scratch): run over a null base it measures, run over d_scratch it carves -- no size
+// formula beside the pointers.  (hipMalloc's alignment exceeds any asked for here, so both runs pad alike.)
+struct Arena {
+    uintptr_t at;
+    explicit Arena(void* p = nullptr) : at(reinterpret_cast<uintptr_t>(p)) {}
+    template <class T> T* take(size_t count, size_t align = alignof(T)) {
+        T* p = reinterpret_cast<T*>(at = (at + align - 1) & ~(uintptr_t)(align - 1));
+        at += count * sizeof(T);
+        return p;
+    }
+    size_t bytes_from(const void* p) const { return at - reinterpret_cast<uintptr_t>(p); }   // from a sub-buffer taken earlier to here
+};
+template <class Layout> int carve_scratch(vp_ctx* c, Layout layout) {
+    Arena measure;
+    layout(measure);                                  // (what it fills now is overwritten below)
+    if (int rc = ensure_scratch(c, measure.bytes_from(nullptr))) return rc;
+    Arena a(c->d_scratch);
+    layout(a);
+    return VP_OK;
+}
+
+// rows [lo, lo + n) of n_total that context i of several works on: contiguous blocks of `per` rows, the last ones short or empty
+std::pair<int, int> block_of(int i, int per, int n_total) { const int lo = std::min(i * per, n_total); return {lo, std::min(lo + per, n_total) - lo}; }
+// steps of a stretch run's chain kept on the device between two copies to the host: 256 MiB worth of rows, at least one
+size_t chain_chunk(int nsteps, size_t row_doubles) {
+    return std::max<size_t>(1, std::min<size_t>((size_t)std::max(nsteps, 1), ((size_t)256 << 20) / (row_doubles * sizeof(double))));
+}
+
 int ensure_pinned(vp_ctx* c, size_t bytes) {
     if (bytes <= c->h_pinned_bytes) return VP_OK;
     if (c->h_pinned) HIP_TRY(c, hipHostFree(c->h_pinned));

@@ -327,16 +327,14 @@ int vp_model_flux_rowsum(vp_ctx* c, int inst, int W, int D, const double* theta,
     HIP_TRY(c, hipSetDevice(c->device));
     if ((rc = ensure_workspace(c, W))) return rc;
     const size_t P = c->inst[inst].dev.P;
-    // scratch: the (W, P) rows | the P weights | the W sums
-    if ((rc = ensure_scratch(c, ((size_t)W * P + P + (size_t)W) * sizeof(double)))) return rc;
-    double* d_w = c->d_scratch + (size_t)W * P;
-    double* d_s = d_w + P;
+    struct Dev { double *rows, *w, *s; } d;       // scratch: the (W, P) rows | the P weights | the W sums
+    if ((rc = carve_scratch(c, [&](Arena& A) { d = Dev{A.take<double>((size_t)W * P), A.take<double>(P), A.take<double>(W)}; }))) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->d_theta, theta, (size_t)W * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d_w, weights, P * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if ((rc = enqueue_model_flux(c, inst, W, c->d_theta, c->d_scratch, convolved, c->stream))) return rc;
-    hipLaunchKernelGGL(row_weighted_sum_kernel, dim3(W), dim3(256), 0, c->stream, c->d_scratch, (int)P, d_w, c0, d_s);
+    HIP_TRY(c, hipMemcpyAsync(d.w, weights, P * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if ((rc = enqueue_model_flux(c, inst, W, c->d_theta, d.rows, convolved, c->stream))) return rc;
+    hipLaunchKernelGGL(row_weighted_sum_kernel, dim3(W), dim3(256), 0, c->stream, d.rows, (int)P, d.w, c0, d.s);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(out, d_s, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out, d.s, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return VP_OK;
 }

@@ -125,7 +125,7 @@ int vp_multi_lnprob_batch(vp_multi* m, int W, int D, const double* theta, double
     std::vector<char> begun(G, 0);                     // whose batch is in flight (its pinned buffer exists and will be written)
     int rc = VP_OK;
     for (int i = 0; i < G && !rc; ++i) {               // every block in flight before any wait
-        const int lo = std::min(i * per, W), n = std::min(lo + per, W) - lo;
+        const auto [lo, n] = block_of(i, per, W);
         vp_ctx* c = m->ctx[i];
         locks.emplace_back(c->mu);
         prearm_cancel(c);
@@ -143,7 +143,7 @@ int vp_multi_lnprob_batch(vp_multi* m, int W, int D, const double* theta, double
     if (rc) return rc;
     for (int i = 0; i < G; ++i) {
         if (!begun[i]) continue;
-        const int lo = std::min(i * per, W), n = std::min(lo + per, W) - lo;
+        const auto [lo, n] = block_of(i, per, W);
         std::memcpy(out + lo, m->ctx[i]->h_pinned + (size_t)n * D, (size_t)n * sizeof(double));
     }
     return VP_OK;
@@ -166,6 +166,26 @@ static int multi_barrier(vp_multi* m) {
     return VP_OK;
 }
 
+// (called with m->mu held) What the sharded samplers check and set up before anything else: a usable vp_multi whose devices map each
+// other's memory, every context locked (`locks`) with its waiting launch sent away, a batch every context accepts, the barrier's events.
+static int multi_sampler_enter(vp_multi* m, const char* who, int W, int D, const double* pos, const double* lnprob,
+                               std::vector<std::unique_lock<std::mutex>>& locks) {
+    if (m->broken) return multi_broken(m);
+    const int G = (int)m->ctx.size();
+    if (G > vp::MAX_REPLICAS) { m->err = std::string(who) + ": at most " + std::to_string(vp::MAX_REPLICAS) + " device contexts"; return VP_EINVAL; }
+    if (m->no_peer) { m->err = std::string(who) + ": the devices cannot map each other's memory (no peer access)"; return VP_ESTATE; }
+    for (int i = 0; i < G; ++i) { locks.emplace_back(m->ctx[i]->mu); prearm_cancel(m->ctx[i]); }
+    for (int i = 0; i < G; ++i)
+        if (int rc = check_batch_args(m->ctx[i], W, D, pos, lnprob)) return multi_fail(m, i, rc);
+    for (int i = (int)m->ev.size(); i < G; ++i) {
+        hipEvent_t e;
+        if (hipSetDevice(m->ctx[i]->device) != hipSuccess || hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess)
+            return multi_fail(m, i, fail(m->ctx[i], VP_EHIP, "hipEventCreate failed"));
+        m->ev.push_back(e);
+    }
+    return VP_OK;
+}
+
 // One ensemble, G device contexts (BASELINE config 4: "2048 zeus walkers sharded over 8 GPUs"; vfit_mcmc.py:425-440,
 // 536-540 fans ONE ensemble over its workers): see csrc/sampler_kernels.h.  Per half-step every context runs its block of
 // the active half -- one walker_kernel launch where vp_stretch_run would use one for the whole half, else propose ->
@@ -175,78 +195,56 @@ int vp_multi_stretch_run(vp_multi* m, int W, int D, double* pos, double* lnprob,
                          uint64_t seed, uint64_t step0, double* chain, double* chain_lnprob, int64_t* naccepted) {
     if (!m) return VP_EINVAL;
     std::lock_guard<std::mutex> g(m->mu);
-    if (m->broken) return multi_broken(m);
-    const int G = (int)m->ctx.size();
-    if (G > vp::MAX_REPLICAS) { m->err = "vp_multi_stretch_run: at most " + std::to_string(vp::MAX_REPLICAS) + " device contexts"; return VP_EINVAL; }
-    if (m->no_peer) { m->err = "vp_multi_stretch_run: the devices cannot map each other's memory (no peer access)"; return VP_ESTATE; }
     std::vector<std::unique_lock<std::mutex>> locks;
-    for (int i = 0; i < G; ++i) { locks.emplace_back(m->ctx[i]->mu); prearm_cancel(m->ctx[i]); }
-    int rc;
-    for (int i = 0; i < G; ++i)
-        if ((rc = check_batch_args(m->ctx[i], W, D, pos, lnprob))) return multi_fail(m, i, rc);
+    int rc = multi_sampler_enter(m, "vp_multi_stretch_run", W, D, pos, lnprob, locks);
+    if (rc) return rc;
+    const int G = (int)m->ctx.size();
     vp_ctx* c0 = m->ctx[0];
-    if (W < 2 || (W & 1)) { c0->err = "vp_multi_stretch_run: the number of walkers must be even and >= 2"; return multi_fail(m, 0, VP_EINVAL); }
-    if (nsteps < 0 || !(a > 1.0)) { c0->err = "vp_multi_stretch_run: nsteps must be >= 0 and a > 1"; return multi_fail(m, 0, VP_EINVAL); }
-    if ((chain == nullptr) != (chain_lnprob == nullptr)) { c0->err = "vp_multi_stretch_run: chain and chain_lnprob go together"; return multi_fail(m, 0, VP_EINVAL); }
-    if (have_lnprob)
-        for (int w = 0; w < W; ++w)
-            if (lnprob[w] != lnprob[w]) { c0->err = "vp_multi_stretch_run: the initial lnprob holds NaN (Probability function returned NaN)"; return multi_fail(m, 0, VP_ENAN); }
-    if ((int)m->ev.size() != G) {
-        for (int i = (int)m->ev.size(); i < G; ++i) {
-            hipEvent_t e;
-            if (hipSetDevice(m->ctx[i]->device) != hipSuccess || hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
-                m->ctx[i]->err = "hipEventCreate failed"; return multi_fail(m, i, VP_EHIP);
-            }
-            m->ev.push_back(e);
-        }
-    }
+    const SlotFail F{m, m->ctx.data(), nullptr};
+    if ((rc = stretch_check_args(c0, "vp_multi_stretch_run", W, nsteps, a, chain, chain_lnprob, have_lnprob, lnprob))) return F.code(0, rc);
     const int half = W / 2, per = (half + G - 1) / G;
     bool one_device = true;
     for (int i = 1; i < G; ++i) one_device = one_device && m->ctx[i]->device == c0->device;
     const bool flags_mode = c0->tune.multi_sync > 0;
-    // device state per context: pos (W,D) | lp (W) | prop (per,D) | lp_new (per) | zz (per) | chain chunk (flags mode: every
-    // context keeps the rows of ITS walkers; events mode: replica 0 snapshots the ensemble) ; nacc (W) | nanflag | flags (G) | done | timeout
     const size_t row = (size_t)W * (D + 1);
-    const size_t chunk = chain ? std::max<size_t>(1, std::min<size_t>((size_t)std::max(nsteps, 1), ((size_t)256 << 20) / (row * sizeof(double)))) : 0;
-    struct Dev { double *pos, *lp, *prop, *lpnew, *zz, *chain; long long* nacc; int *nan, *flags, *timeout; unsigned int* done; };
+    const size_t chunk = chain ? chain_chunk(nsteps, row) : 0;
+    struct Dev { double *pos, *lp, *prop, *lpnew, *zz, *chain; long long* nacc; int *nan, *flags, *timeout; unsigned int* done; size_t zeroed; };
     std::vector<Dev> dv(G);
     for (int i = 0; i < G; ++i) {
         vp_ctx* c = m->ctx[i];
-#define MTRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { c->err = std::string(#expr) + ": " + hipGetErrorString(e__); return multi_fail(m, i, VP_EHIP); } } while (0)
-        MTRY(hipSetDevice(c->device));
-        if ((rc = ensure_workspace(c, std::max(W, per)))) return multi_fail(m, i, rc);
-        const size_t nchain = (flags_mode || i == 0) ? chunk * row : 0;
-        const size_t nd = (size_t)W * D + W + (size_t)per * D + 2 * (size_t)per + nchain;
-        if ((rc = ensure_scratch(c, nd * sizeof(double) + (size_t)W * sizeof(long long) + (vp::MAX_REPLICAS + 4 + vp::PUB_GROUPS + 1) * sizeof(int) + 64))) return multi_fail(m, i, rc);
+        SLOT_TRY(F, i, hipSetDevice(c->device));
+        if ((rc = ensure_workspace(c, std::max(W, per)))) return F.code(i, rc);
         Dev& d = dv[i];
-        d.pos = c->d_scratch; d.lp = d.pos + (size_t)W * D; d.prop = d.lp + W; d.lpnew = d.prop + (size_t)per * D;
-        d.zz = d.lpnew + per; d.chain = d.zz + per;
-        d.nacc = reinterpret_cast<long long*>(d.chain + nchain);
-        d.nan = reinterpret_cast<int*>(d.nacc + W);
-        d.flags = d.nan + 1; d.done = reinterpret_cast<unsigned int*>(d.flags + vp::MAX_REPLICAS);      // (PUB_GROUPS + 1 counters)
-        d.timeout = reinterpret_cast<int*>(d.done + vp::PUB_GROUPS + 1);
-        MTRY(hipMemcpyAsync(d.pos, pos, (size_t)W * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        MTRY(hipMemsetAsync(d.nacc, 0, (size_t)W * sizeof(long long) + (vp::MAX_REPLICAS + 4 + vp::PUB_GROUPS + 1) * sizeof(int), c->stream));
-        if (have_lnprob) MTRY(hipMemcpyAsync(d.lp, lnprob, (size_t)W * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        if ((rc = carve_scratch(c, [&](Arena& A) {
+            d.pos = A.take<double>((size_t)W * D); d.lp = A.take<double>(W);
+            d.prop = A.take<double>((size_t)per * D); d.lpnew = A.take<double>(per); d.zz = A.take<double>(per);
+            // chain chunk (flags mode: every context keeps the rows of ITS walkers; events mode: replica 0 snapshots the ensemble)
+            d.chain = A.take<double>((flags_mode || i == 0) ? chunk * row : 0);
+            // nacc (W) | nanflag | flags | done (PUB_GROUPS + 1 counters) | timeout: cleared by ONE memset
+            d.nacc = A.take<long long>(W); d.nan = A.take<int>(1); d.flags = A.take<int>(vp::MAX_REPLICAS);
+            d.done = A.take<unsigned int>(vp::PUB_GROUPS + 1); d.timeout = A.take<int>(1); d.zeroed = A.bytes_from(d.nacc);
+        }))) return F.code(i, rc);
+        SLOT_TRY(F, i, hipMemcpyAsync(d.pos, pos, (size_t)W * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        SLOT_TRY(F, i, hipMemsetAsync(d.nacc, 0, d.zeroed, c->stream));
+        if (have_lnprob) SLOT_TRY(F, i, hipMemcpyAsync(d.lp, lnprob, (size_t)W * sizeof(double), hipMemcpyHostToDevice, c->stream));
         else {
             // every replica evaluates the whole start state itself (once per run; the same launches as vp_stretch_run's)
-            if ((rc = enqueue_lnprob(c, W, d.pos, d.lp, c->stream))) return multi_fail(m, i, rc);
+            if ((rc = enqueue_lnprob(c, W, d.pos, d.lp, c->stream))) return F.code(i, rc);
             hipLaunchKernelGGL(vp::nan_flag_kernel, dim3((W + 255) / 256), dim3(256), 0, c->stream, d.lp, W, d.nan);
         }
     }
     if (!have_lnprob) {
         int h_nan0 = 0;
-        vp_ctx* c = c0; const int i = 0;
-        MTRY(hipSetDevice(c->device));
-        MTRY(hipMemcpyAsync(&h_nan0, dv[0].nan, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        MTRY(hipStreamSynchronize(c->stream));
-        if (h_nan0) { c0->err = "vp_multi_stretch_run: the initial lnprob holds NaN (Probability function returned NaN)"; return multi_fail(m, 0, VP_ENAN); }
+        SLOT_TRY(F, 0, hipSetDevice(c0->device));
+        SLOT_TRY(F, 0, hipMemcpyAsync(&h_nan0, dv[0].nan, sizeof(int), hipMemcpyDeviceToHost, c0->stream));
+        SLOT_TRY(F, 0, hipStreamSynchronize(c0->stream));
+        if (h_nan0) return F(0, VP_ENAN, "vp_multi_stretch_run: the initial lnprob holds NaN (Probability function returned NaN)");
     }
     // every replica's start state (and its zeroed flags) is in place before any kernel of the run starts
     for (int i = 0; i < G; ++i) {
         vp_ctx* c = m->ctx[i];
-        MTRY(hipSetDevice(c->device));
-        MTRY(hipStreamSynchronize(c->stream));
+        SLOT_TRY(F, i, hipSetDevice(c->device));
+        SLOT_TRY(F, i, hipStreamSynchronize(c->stream));
     }
     const int thr = 64;
     std::vector<double> h_chunk;                       // flags mode: one context's chain chunk on its way to the caller's arrays
@@ -260,8 +258,8 @@ int vp_multi_stretch_run(vp_multi* m, int W, int D, double* pos, double* lnprob,
                 ++seq;
                 for (int i = 0; i < G; ++i) {
                     vp_ctx* c = m->ctx[i];
-                    const int k0 = std::min(i * per, half), nk = std::min(k0 + per, half) - k0;
-                    MTRY(hipSetDevice(c->device));
+                    const auto [k0, nk] = block_of(i, per, half);
+                    SLOT_TRY(F, i, hipSetDevice(c->device));
                     const Dev& d = dv[i];
                     vp::Replicas R{};
                     R.n = G;
@@ -287,50 +285,47 @@ int vp_multi_stretch_run(vp_multi* m, int W, int D, double* pos, double* lnprob,
                     } else {
                         hipLaunchKernelGGL(vp::stretch_propose_block_kernel, dim3((nk + thr - 1) / thr), dim3(thr), 0, c->stream, d.pos, D, s0,
                                            half, cc0, half, a, seed, step, h, k0, nk, d.prop, d.zz, R);
-                        if ((rc = enqueue_lnprob(c, nk, d.prop, d.lpnew, c->stream, half))) return multi_fail(m, i, rc);
+                        if ((rc = enqueue_lnprob(c, nk, d.prop, d.lpnew, c->stream, half))) return F.code(i, rc);
                         hipLaunchKernelGGL(vp::stretch_accept_block_kernel, dim3((nk + thr - 1) / thr), dim3(thr), 0, c->stream, d.pos, d.lp, R,
                                            d.prop, d.lpnew, d.zz, D, s0, k0, nk, seed, step, h, d.nacc, d.nan, cp, cl);
                     }
-                    MTRY(hipGetLastError());
+                    SLOT_TRY(F, i, hipGetLastError());
                 }
-                if (!flags_mode && (rc = multi_barrier(m))) return multi_fail(m, 0, rc);
+                if (!flags_mode && (rc = multi_barrier(m))) return F.code(0, rc);
             }
             if (chain && !flags_mode) {
-                vp_ctx* c = c0; const int i = 0;
-                MTRY(hipSetDevice(c->device));
-                MTRY(hipMemcpyAsync(dv[0].chain + (size_t)it * W * D, dv[0].pos, (size_t)W * D * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-                MTRY(hipMemcpyAsync(dv[0].chain + chunk * (size_t)W * D + (size_t)it * W, dv[0].lp, (size_t)W * sizeof(double),
-                                    hipMemcpyDeviceToDevice, c->stream));
+                SLOT_TRY(F, 0, hipSetDevice(c0->device));
+                SLOT_TRY(F, 0, hipMemcpyAsync(dv[0].chain + (size_t)it * W * D, dv[0].pos, (size_t)W * D * sizeof(double), hipMemcpyDeviceToDevice, c0->stream));
+                SLOT_TRY(F, 0, hipMemcpyAsync(dv[0].chain + chunk * (size_t)W * D + (size_t)it * W, dv[0].lp, (size_t)W * sizeof(double),
+                                             hipMemcpyDeviceToDevice, c0->stream));
                 // nobody writes into replica 0 (the next half-step's moved rows) before this snapshot is taken
-                MTRY(hipEventRecord(m->ev[0], c->stream));
+                SLOT_TRY(F, 0, hipEventRecord(m->ev[0], c0->stream));
                 for (int j = 1; j < G; ++j) {
                     vp_ctx* cj = m->ctx[j];
-                    if (hipSetDevice(cj->device) != hipSuccess || hipStreamWaitEvent(cj->stream, m->ev[0], 0) != hipSuccess) {
-                        cj->err = "hipStreamWaitEvent failed"; return multi_fail(m, j, VP_EHIP);
-                    }
+                    if (hipSetDevice(cj->device) != hipSuccess || hipStreamWaitEvent(cj->stream, m->ev[0], 0) != hipSuccess)
+                        return F(j, VP_EHIP, "hipStreamWaitEvent failed");
                 }
             }
         }
         if (chain && !flags_mode) {
-            vp_ctx* c = c0; const int i = 0;
-            MTRY(hipSetDevice(c->device));
-            MTRY(hipMemcpyAsync(chain + (size_t)done * W * D, dv[0].chain, (size_t)n * W * D * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-            MTRY(hipMemcpyAsync(chain_lnprob + (size_t)done * W, dv[0].chain + chunk * (size_t)W * D, (size_t)n * W * sizeof(double),
-                                hipMemcpyDeviceToHost, c->stream));
-            MTRY(hipStreamSynchronize(c->stream));
+            SLOT_TRY(F, 0, hipSetDevice(c0->device));
+            SLOT_TRY(F, 0, hipMemcpyAsync(chain + (size_t)done * W * D, dv[0].chain, (size_t)n * W * D * sizeof(double), hipMemcpyDeviceToHost, c0->stream));
+            SLOT_TRY(F, 0, hipMemcpyAsync(chain_lnprob + (size_t)done * W, dv[0].chain + chunk * (size_t)W * D, (size_t)n * W * sizeof(double),
+                                         hipMemcpyDeviceToHost, c0->stream));
+            SLOT_TRY(F, 0, hipStreamSynchronize(c0->stream));
         }
         if (chain && flags_mode) {
             // every context holds the chain rows of the walkers it moves (blocks k0 ... of both halves): merged here
             h_chunk.resize((size_t)n * row);
             for (int i = 0; i < G; ++i) {
                 vp_ctx* c = m->ctx[i];
-                const int k0 = std::min(i * per, half), nk = std::min(k0 + per, half) - k0;
+                const auto [k0, nk] = block_of(i, per, half);
                 if (nk <= 0) continue;
-                MTRY(hipSetDevice(c->device));
-                MTRY(hipMemcpyAsync(h_chunk.data(), dv[i].chain, (size_t)n * W * D * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-                MTRY(hipMemcpyAsync(h_chunk.data() + (size_t)n * W * D, dv[i].chain + chunk * (size_t)W * D, (size_t)n * W * sizeof(double),
-                                    hipMemcpyDeviceToHost, c->stream));
-                MTRY(hipStreamSynchronize(c->stream));
+                SLOT_TRY(F, i, hipSetDevice(c->device));
+                SLOT_TRY(F, i, hipMemcpyAsync(h_chunk.data(), dv[i].chain, (size_t)n * W * D * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+                SLOT_TRY(F, i, hipMemcpyAsync(h_chunk.data() + (size_t)n * W * D, dv[i].chain + chunk * (size_t)W * D, (size_t)n * W * sizeof(double),
+                                             hipMemcpyDeviceToHost, c->stream));
+                SLOT_TRY(F, i, hipStreamSynchronize(c->stream));
                 for (int t = 0; t < n; ++t)
                     for (int hh = 0; hh < 2; ++hh) {
                         const size_t w0 = (size_t)hh * half + k0;
@@ -347,31 +342,30 @@ int vp_multi_stretch_run(vp_multi* m, int W, int D, double* pos, double* lnprob,
     std::vector<long long> h_nacc(W);
     for (int i = 0; i < G; ++i) {                      // (flags mode: replica 0 is complete only when every context is through)
         vp_ctx* c = m->ctx[i];
-        MTRY(hipSetDevice(c->device));
-        MTRY(hipStreamSynchronize(c->stream));
+        SLOT_TRY(F, i, hipSetDevice(c->device));
+        SLOT_TRY(F, i, hipStreamSynchronize(c->stream));
     }
     for (int i = 0; i < G; ++i) {
         vp_ctx* c = m->ctx[i];
-        MTRY(hipSetDevice(c->device));
+        SLOT_TRY(F, i, hipSetDevice(c->device));
         int h_nan = 0, h_to = 0;
-        MTRY(hipMemcpyAsync(&h_nan, dv[i].nan, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        MTRY(hipMemcpyAsync(&h_to, dv[i].timeout, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        MTRY(hipMemcpyAsync(h_nacc.data(), dv[i].nacc, (size_t)W * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+        SLOT_TRY(F, i, hipMemcpyAsync(&h_nan, dv[i].nan, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        SLOT_TRY(F, i, hipMemcpyAsync(&h_to, dv[i].timeout, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        SLOT_TRY(F, i, hipMemcpyAsync(h_nacc.data(), dv[i].nacc, (size_t)W * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
         if (i == 0) {
-            MTRY(hipMemcpyAsync(pos, dv[0].pos, (size_t)W * D * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-            MTRY(hipMemcpyAsync(lnprob, dv[0].lp, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            SLOT_TRY(F, i, hipMemcpyAsync(pos, dv[0].pos, (size_t)W * D * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            SLOT_TRY(F, i, hipMemcpyAsync(lnprob, dv[0].lp, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         }
-        MTRY(hipStreamSynchronize(c->stream));
+        SLOT_TRY(F, i, hipStreamSynchronize(c->stream));
         any_nan |= h_nan; any_timeout |= h_to;
         if (naccepted) {
-            const int k0 = std::min(i * per, half), nk = std::min(k0 + per, half) - k0;
+            const auto [k0, nk] = block_of(i, per, half);
             for (int hh = 0; hh < 2; ++hh)
                 for (int k = k0; k < k0 + nk; ++k) naccepted[hh * half + k] += (int64_t)h_nacc[hh * half + k];
         }
     }
-#undef MTRY
-    if (any_timeout) { c0->err = "vp_multi_stretch_run: a context gave up waiting for its peers' half-step (in-kernel flags; try the multi_sync = 0 option)"; return multi_fail(m, 0, VP_ESTATE); }
-    if (any_nan) { c0->err = "vp_multi_stretch_run: Probability function returned NaN"; return multi_fail(m, 0, VP_ENAN); }
+    if (any_timeout) return F(0, VP_ESTATE, "vp_multi_stretch_run: a context gave up waiting for its peers' half-step (in-kernel flags; try the multi_sync = 0 option)");
+    if (any_nan) return F(0, VP_ENAN, "vp_multi_stretch_run: Probability function returned NaN");
     return VP_OK;
 }
 
@@ -380,21 +374,9 @@ int vp_multi_slice_run(vp_multi* m, int W, int D, double* pos, double* lnprob, i
                        double* chain, double* chain_lnprob, double* mu_history, int64_t* n_evals) {
     if (!m) return VP_EINVAL;
     std::lock_guard<std::mutex> g(m->mu);
-    if (m->broken) return multi_broken(m);
-    const int G = (int)m->ctx.size();
-    if (G > vp::MAX_REPLICAS) { m->err = "vp_multi_slice_run: at most " + std::to_string(vp::MAX_REPLICAS) + " device contexts"; return VP_EINVAL; }
-    if (m->no_peer) { m->err = "vp_multi_slice_run: the devices cannot map each other's memory (no peer access)"; return VP_ESTATE; }
     std::vector<std::unique_lock<std::mutex>> locks;
-    for (int i = 0; i < G; ++i) { locks.emplace_back(m->ctx[i]->mu); prearm_cancel(m->ctx[i]); }
-    for (int i = 0; i < G; ++i)
-        if (int rc = check_batch_args(m->ctx[i], W, D, pos, lnprob)) return multi_fail(m, i, rc);
-    for (int i = (int)m->ev.size(); i < G; ++i) {
-        hipEvent_t e;
-        if (hipSetDevice(m->ctx[i]->device) != hipSuccess || hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
-            m->ctx[i]->err = "hipEventCreate failed"; return multi_fail(m, i, VP_EHIP);
-        }
-        m->ev.push_back(e);
-    }
+    if (int rc = multi_sampler_enter(m, "vp_multi_slice_run", W, D, pos, lnprob, locks)) return rc;
+    const int G = (int)m->ctx.size();
     int bad = 0;
     const int rc = slice_run_impl(m, m->ctx.data(), G, W, D, pos, lnprob, have_lnprob, nsteps, mu, tune, tolerance, patience, maxsteps,
                                   seed, step0, chain, chain_lnprob, mu_history, n_evals, &bad);

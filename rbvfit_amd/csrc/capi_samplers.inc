@@ -1,50 +1,61 @@
 // capi_samplers.inc -- entry points: device-resident stretch-move and slice samplers (vp_stretch_run, vp_slice_run).
 // A fragment of the ONE translation unit capi.hip (included there inside extern "C", in order; not a header of its own).
+namespace {
+// what both stretch entries ask of their arguments (`w`: the entry's name); the message is left in c
+int stretch_check_args(vp_ctx* c, const std::string& w, int W, int nsteps, double a, const double* chain, const double* chain_lnprob,
+                       int have_lnprob, const double* lnprob) {
+    if (W < 2 || (W & 1)) return fail(c, VP_EINVAL, w + ": the number of walkers must be even and >= 2");
+    if (nsteps < 0 || !(a > 1.0)) return fail(c, VP_EINVAL, w + ": nsteps must be >= 0 and a > 1");
+    if ((chain == nullptr) != (chain_lnprob == nullptr)) return fail(c, VP_EINVAL, w + ": chain and chain_lnprob go together");
+    for (int k = 0; have_lnprob && k < W; ++k)
+        if (lnprob[k] != lnprob[k]) return fail(c, VP_ENAN, w + ": the initial lnprob holds NaN (Probability function returned NaN)");
+    return VP_OK;
+}
+}  // namespace
+static int multi_barrier(vp_multi* m);
+static int multi_fail(vp_multi* m, int i, int rc);
+// How a sampler that drives several contexts fails on slot i of them: that context gets the message; a vp_multi entry point
+// (bad == NULL) returns through multi_fail ("device slot i: ..."), slice_run_impl tells its caller the slot, which does the same.
+struct SlotFail {
+    vp_multi* m; vp_ctx* const* cx; int* bad;
+    int code(int i, int rc) const { if (!bad) return multi_fail(m, i, rc); *bad = i; return rc; }
+    int operator()(int i, int rc, const std::string& msg) const { return code(i, fail(cx[i], rc, msg)); }
+};
+#define SLOT_TRY(F, i, expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) return (F)((i), VP_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__)); } while (0)
+
 int vp_stretch_run(vp_ctx* c, int W, int D, double* pos, double* lnprob, int have_lnprob, int nsteps, double a,
                    uint64_t seed, uint64_t step0, double* chain, double* chain_lnprob, int64_t* naccepted) {
     if (!c) return VP_EINVAL;
     CtxGuard g(c);
     int rc = check_batch_args(c, W, D, pos, lnprob);
-    if (rc) return rc;
-    if (W < 2 || (W & 1)) return fail(c, VP_EINVAL, "vp_stretch_run: the number of walkers must be even and >= 2");
-    if (nsteps < 0 || !(a > 1.0)) return fail(c, VP_EINVAL, "vp_stretch_run: nsteps must be >= 0 and a > 1");
-    if ((chain == nullptr) != (chain_lnprob == nullptr)) return fail(c, VP_EINVAL, "vp_stretch_run: chain and chain_lnprob go together");
+    if (rc || (rc = stretch_check_args(c, "vp_stretch_run", W, nsteps, a, chain, chain_lnprob, have_lnprob, lnprob))) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     if ((rc = ensure_workspace(c, W))) return rc;
     hipStream_t s = c->stream;
     const int half = W / 2;
-    // device state: pos (W,D) | lp (W) | prop (half,D) | lp_new (half) | zz (half) | second buffer of pos, lp (overlapped half-steps) |
-    //               chain chunk | nacc (W) | nanflag, timeout | versions (W)
-    //               mailbox lines 2 x W x 8 (overlapped half-steps with D <= 6: row, lnprob, version in one 64-byte line) |
-    const size_t nd_state = (size_t)W * D + W + (size_t)half * D + 2 * (size_t)half + (size_t)W * D + W + 8 + 2 * (size_t)W * 8;
     const size_t row = (size_t)W * (D + 1);                       // doubles stored per step
-    size_t chunk = chain ? std::max<size_t>(1, std::min<size_t>((size_t)std::max(nsteps, 1), ((size_t)256 << 20) / (row * sizeof(double)))) : 0;
-    const size_t bytes = (nd_state + chunk * row) * sizeof(double) + (size_t)W * sizeof(long long) + 64 + (size_t)W * sizeof(int);
-    if ((rc = ensure_scratch(c, bytes))) return rc;
-    double* d_pos = c->d_scratch;
-    double* d_lp = d_pos + (size_t)W * D;
-    double* d_prop = d_lp + W;
-    double* d_lpnew = d_prop + (size_t)half * D;
-    double* d_zz = d_lpnew + half;
-    double* d_pos1 = d_zz + half;                                 // the rows' second buffer (overlapped half-steps)
-    double* d_lp1 = d_pos1 + (size_t)W * D;
-    double* d_mail = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(d_lp1 + W) + 63) & ~(uintptr_t)63);    // 64-byte aligned lines
-    double* d_chain = d_mail + 2 * (size_t)W * 8;                 // chunk * (W*D) then chunk * W
-    long long* d_nacc = reinterpret_cast<long long*>(d_chain + chunk * row);
-    int* d_nan = reinterpret_cast<int*>(d_nacc + W);             // [0] NaN flag, [1] a device-side wait gave up
-    int* d_ver = d_nan + 16;                                      // (W) versions
-    HIP_TRY(c, hipMemcpyAsync(d_pos, pos, (size_t)W * D * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemsetAsync(d_nacc, 0, (size_t)W * sizeof(long long) + 64 + (size_t)W * sizeof(int), s));
+    const size_t chunk = chain ? chain_chunk(nsteps, row) : 0;
+    struct Dev { double *pos, *lp, *prop, *lpnew, *zz, *pos1, *lp1, *mail, *chain; long long* nacc; int *nan, *ver; size_t zeroed; } d;
+    if ((rc = carve_scratch(c, [&](Arena& A) {
+        d.pos = A.take<double>((size_t)W * D); d.lp = A.take<double>(W);
+        d.prop = A.take<double>((size_t)half * D); d.lpnew = A.take<double>(half); d.zz = A.take<double>(half);
+        d.pos1 = A.take<double>((size_t)W * D); d.lp1 = A.take<double>(W);     // the rows' second buffer (overlapped half-steps)
+        // mailbox lines 2 x W x 8 (overlapped half-steps with D <= 6: row, lnprob, version in one 64-byte line)
+        d.mail = A.take<double>(2 * (size_t)W * 8, 64);
+        d.chain = A.take<double>(chunk * row);                     // chunk * (W*D) then chunk * W
+        // nacc (W) | flags: [0] NaN, [1] a device-side wait gave up | versions (W): cleared by ONE memset
+        d.nacc = A.take<long long>(W); d.nan = A.take<int>(16); d.ver = A.take<int>(W); d.zeroed = A.bytes_from(d.nacc);
+    }))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(d.pos, pos, (size_t)W * D * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemsetAsync(d.nacc, 0, d.zeroed, s));
     if (have_lnprob) {
-        for (int w = 0; w < W; ++w)
-            if (lnprob[w] != lnprob[w]) return fail(c, VP_ENAN, "vp_stretch_run: the initial lnprob holds NaN (Probability function returned NaN)");
-        HIP_TRY(c, hipMemcpyAsync(d_lp, lnprob, (size_t)W * sizeof(double), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(d.lp, lnprob, (size_t)W * sizeof(double), hipMemcpyHostToDevice, s));
     } else {
         // a walker that starts at NaN would never move (log u < NaN is false) and the run would still report success
-        if ((rc = enqueue_lnprob(c, W, d_pos, d_lp, s))) return rc;
-        hipLaunchKernelGGL(vp::nan_flag_kernel, dim3((W + 255) / 256), dim3(256), 0, s, d_lp, W, d_nan);
+        if ((rc = enqueue_lnprob(c, W, d.pos, d.lp, s))) return rc;
+        hipLaunchKernelGGL(vp::nan_flag_kernel, dim3((W + 255) / 256), dim3(256), 0, s, d.lp, W, d.nan);
         int h_nan0 = 0;
-        HIP_TRY(c, hipMemcpyAsync(&h_nan0, d_nan, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(&h_nan0, d.nan, sizeof(int), hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
         if (h_nan0) return fail(c, VP_ENAN, "vp_stretch_run: the initial lnprob holds NaN (Probability function returned NaN)");
     }
@@ -77,14 +88,14 @@ int vp_stretch_run(vp_ctx* c, int W, int D, double* pos, double* lnprob, int hav
         std::vector<double> lp0(W);
         if (have_lnprob) std::memcpy(lp0.data(), lnprob, (size_t)W * sizeof(double));
         else {
-            HIP_TRY(c, hipMemcpyAsync(lp0.data(), d_lp, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipMemcpyAsync(lp0.data(), d.lp, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, s));
             HIP_TRY(c, hipStreamSynchronize(s));
         }
         for (int w = 0; w < W; ++w) {
             std::memcpy(&h_mail[(size_t)w * 8], pos + (size_t)w * D, (size_t)D * sizeof(double));
             h_mail[(size_t)w * 8 + 6] = lp0[w];                    // ([7]: version 0 = all-zero bits)
         }
-        HIP_TRY(c, hipMemcpyAsync(d_mail, h_mail.data(), h_mail.size() * sizeof(double), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(d.mail, h_mail.data(), h_mail.size() * sizeof(double), hipMemcpyHostToDevice, s));
     }
     hipStream_t s2 = ovl ? c->stream2 : s;
     // (whatever way this call ends -- an error return from the middle of the loop included -- nothing of it is left running on the
@@ -102,17 +113,17 @@ int vp_stretch_run(vp_ctx* c, int W, int D, double* pos, double* lnprob, int hav
                 const int s0 = h ? half : 0, c0 = h ? 0 : half;
                 if (one_launch) {
                     vp::StretchArgs sa{};
-                    sa.pos = d_pos; sa.lp = d_lp; sa.nacc = d_nacc; sa.nanflag = d_nan;
-                    sa.chain_pos = chain ? d_chain + (size_t)it * W * D : (double*)nullptr;
-                    sa.chain_lp = chain ? d_chain + chunk * (size_t)W * D + (size_t)it * W : (double*)nullptr;
+                    sa.pos = d.pos; sa.lp = d.lp; sa.nacc = d.nacc; sa.nanflag = d.nan;
+                    sa.chain_pos = chain ? d.chain + (size_t)it * W * D : (double*)nullptr;
+                    sa.chain_lp = chain ? d.chain + chunk * (size_t)W * D + (size_t)it * W : (double*)nullptr;
                     sa.a = a; sa.seed = seed; sa.step = step; sa.s0 = s0; sa.c0 = c0; sa.nC = half; sa.half = h;
                     if (ovl) {
                         // every walker has been updated k = done + it times when this step begins (the first half once more when
                         // h = 1): rows live in buffer (update count) & 1
                         const int k = done + it, t = 2 * k + h;
-                        double* pb[2] = {mail ? d_mail : d_pos, mail ? d_mail + (size_t)W * 8 : d_pos1};
-                        double* lb2[2] = {d_lp, d_lp1};
-                        sa.ovl = mail ? 2 : 1; sa.need = t; sa.mine = t + 1; sa.ver = d_ver; sa.timeout = d_nan + 1;
+                        double* pb[2] = {mail ? d.mail : d.pos, mail ? d.mail + (size_t)W * 8 : d.pos1};
+                        double* lb2[2] = {d.lp, d.lp1};
+                        sa.ovl = mail ? 2 : 1; sa.need = t; sa.mine = t + 1; sa.ver = d.ver; sa.timeout = d.nan + 1;
                         sa.pos_x = pb[k & 1]; sa.lp_x = lb2[k & 1];
                         sa.pos_w = pb[(k + 1) & 1]; sa.lp_w = lb2[(k + 1) & 1];
                         sa.pos_c = pb[(h ? k + 1 : k) & 1];
@@ -123,23 +134,23 @@ int vp_stretch_run(vp_ctx* c, int W, int D, double* pos, double* lnprob, int hav
                     continue;
                 }
                 if (!have_prop)
-                    hipLaunchKernelGGL(vp::stretch_propose_kernel, dim3((half + thr - 1) / thr), dim3(thr), 0, s, d_pos, D, s0,
-                                       half, c0, half, a, seed, step, h, d_prop, d_zz);
-                if ((rc = enqueue_lnprob(c, half, d_prop, d_lpnew, s))) return rc;
+                    hipLaunchKernelGGL(vp::stretch_propose_kernel, dim3((half + thr - 1) / thr), dim3(thr), 0, s, d.pos, D, s0,
+                                       half, c0, half, a, seed, step, h, d.prop, d.zz);
+                if ((rc = enqueue_lnprob(c, half, d.prop, d.lpnew, s))) return rc;
                 const bool store = chain && h == 1;
-                double* cp = store ? d_chain + (size_t)it * W * D : (double*)nullptr;
-                double* cl = store ? d_chain + chunk * (size_t)W * D + (size_t)it * W : (double*)nullptr;
+                double* cp = store ? d.chain + (size_t)it * W * D : (double*)nullptr;
+                double* cl = store ? d.chain + chunk * (size_t)W * D + (size_t)it * W : (double*)nullptr;
                 const bool last = (h == 1) && (done + it + 1 == nsteps);
                 if (fuse && !last) {
                     vp::NextProposal nx;
                     nx.half = 1 - h; nx.s0 = nx.half ? half : 0; nx.c0 = nx.half ? 0 : half; nx.nS = half; nx.nC = half;
                     nx.step = h ? step + 1 : step;
-                    hipLaunchKernelGGL(vp::stretch_accept_propose_kernel, dim3(1), dim3(wthr), 0, s, d_pos, d_lp, d_prop,
-                                       d_lpnew, d_zz, W, D, s0, half, seed, step, h, d_nacc, d_nan, cp, cl, a, nx);
+                    hipLaunchKernelGGL(vp::stretch_accept_propose_kernel, dim3(1), dim3(wthr), 0, s, d.pos, d.lp, d.prop,
+                                       d.lpnew, d.zz, W, D, s0, half, seed, step, h, d.nacc, d.nan, cp, cl, a, nx);
                     have_prop = true;
                 } else {
-                    hipLaunchKernelGGL(vp::stretch_accept_kernel, dim3((W + thr - 1) / thr), dim3(thr), 0, s, d_pos, d_lp, d_prop,
-                                       d_lpnew, d_zz, W, D, s0, half, seed, step, h, d_nacc, d_nan, cp, cl);
+                    hipLaunchKernelGGL(vp::stretch_accept_kernel, dim3((W + thr - 1) / thr), dim3(thr), 0, s, d.pos, d.lp, d.prop,
+                                       d.lpnew, d.zz, W, D, s0, half, seed, step, h, d.nacc, d.nan, cp, cl);
                     have_prop = false;
                 }
             }
@@ -150,8 +161,8 @@ int vp_stretch_run(vp_ctx* c, int W, int D, double* pos, double* lnprob, int hav
             HIP_TRY(c, hipStreamWaitEvent(s, c->ev_join, 0));
         }
         if (chain) {
-            HIP_TRY(c, hipMemcpyAsync(chain + (size_t)done * W * D, d_chain, (size_t)n * W * D * sizeof(double), hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipMemcpyAsync(chain_lnprob + (size_t)done * W, d_chain + chunk * (size_t)W * D, (size_t)n * W * sizeof(double),
+            HIP_TRY(c, hipMemcpyAsync(chain + (size_t)done * W * D, d.chain, (size_t)n * W * D * sizeof(double), hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipMemcpyAsync(chain_lnprob + (size_t)done * W, d.chain + chunk * (size_t)W * D, (size_t)n * W * sizeof(double),
                                       hipMemcpyDeviceToHost, s));
             HIP_TRY(c, hipStreamSynchronize(s));      // (the host waits: the next chunk's launches are enqueued behind the copies)
         }
@@ -161,13 +172,13 @@ int vp_stretch_run(vp_ctx* c, int W, int D, double* pos, double* lnprob, int hav
     int h_flags[2] = {0, 0};
     // (overlapped half-steps: after nsteps updates the rows are in buffer nsteps & 1)
     if (mail) {
-        HIP_TRY(c, hipMemcpyAsync(h_mail.data(), d_mail + (size_t)(nsteps & 1) * W * 8, (size_t)W * 8 * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(h_mail.data(), d.mail + (size_t)(nsteps & 1) * W * 8, (size_t)W * 8 * sizeof(double), hipMemcpyDeviceToHost, s));
     } else {
-        HIP_TRY(c, hipMemcpyAsync(pos, (ovl && (nsteps & 1)) ? d_pos1 : d_pos, (size_t)W * D * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(lnprob, (ovl && (nsteps & 1)) ? d_lp1 : d_lp, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(pos, (ovl && (nsteps & 1)) ? d.pos1 : d.pos, (size_t)W * D * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(lnprob, (ovl && (nsteps & 1)) ? d.lp1 : d.lp, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, s));
     }
-    HIP_TRY(c, hipMemcpyAsync(h_nacc.data(), d_nacc, (size_t)W * sizeof(long long), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(h_flags, d_nan, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(h_nacc.data(), d.nacc, (size_t)W * sizeof(long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(h_flags, d.nan, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     if (mail)
         for (int w = 0; w < W; ++w) {
@@ -186,7 +197,6 @@ int vp_stretch_run(vp_ctx* c, int W, int D, double* pos, double* lnprob, int hav
 // into blocks of ceil(B / G) rows, one per context, evaluated with the launch structure the whole batch would get
 // (LaunchPlan::Wp), and written into EVERY replica's result vector (one double per row through peer-mapped pointers), followed
 // by the event barrier.  The replicas therefore stay identical bit for bit, and equal to the single-context run.
-static int multi_barrier(vp_multi* m);
 namespace { __global__ void scatter_rows_kernel(const double* __restrict__ src, int n, int lo, vp::Replicas R) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
@@ -200,13 +210,12 @@ static int slice_run_impl(vp_multi* m, vp_ctx* const* cx, int G, int W, int D, d
     *bad = 0;
     vp_ctx* c = cx[0];
     int rc;
-#define SFAIL(i, code, msg) do { *bad = (i); return fail(cx[i], (code), (msg)); } while (0)
-#define STRY(i, expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) SFAIL(i, VP_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__)); } while (0)
+    const SlotFail F{m, cx, bad};
     if (W < 4 || (W & 1) || W > 2 * vp::SLICE_MAX_HALF)
-        SFAIL(0, VP_EINVAL, "vp_slice_run: the number of walkers must be even, >= 4 and <= " + std::to_string(2 * vp::SLICE_MAX_HALF));
+        return F(0, VP_EINVAL, "vp_slice_run: the number of walkers must be even, >= 4 and <= " + std::to_string(2 * vp::SLICE_MAX_HALF));
     if (nsteps < 0 || !mu || !(*mu > 0.0) || !tune || maxsteps < 1 || patience < 1 || !(tolerance >= 0.0))
-        SFAIL(0, VP_EINVAL, "vp_slice_run: nsteps >= 0, mu > 0, maxsteps >= 1, patience >= 1, tolerance >= 0 and non-NULL mu/tune required");
-    if ((chain == nullptr) != (chain_lnprob == nullptr)) SFAIL(0, VP_EINVAL, "vp_slice_run: chain and chain_lnprob go together");
+        return F(0, VP_EINVAL, "vp_slice_run: nsteps >= 0, mu > 0, maxsteps >= 1, patience >= 1, tolerance >= 0 and non-NULL mu/tune required");
+    if ((chain == nullptr) != (chain_lnprob == nullptr)) return F(0, VP_EINVAL, "vp_slice_run: chain and chain_lnprob go together");
     const int half = W / 2;
     // rows of every round's lnprob batch (the round kernel keeps one slice parameter per row in LDS: <= 4096 rows)
     const int B = std::min(2 * vp::SLICE_MAX_HALF, std::max(2, std::min(8, c->tune.slice_rows)) * half);
@@ -217,60 +226,53 @@ static int slice_run_impl(vp_multi* m, vp_ctx* const* cx, int G, int W, int D, d
     size_t seg = std::min<size_t>((size_t)std::max(nsteps, 1), ((size_t)64 << 20) / ((size_t)W * sizeof(int)));
     if (chain) seg = std::min(seg, std::max<size_t>(1, ((size_t)256 << 20) / (row * sizeof(double))));
     if (c->tune.slice_seg > 0) seg = std::min(seg, (size_t)c->tune.slice_seg);
-    // device state (doubles first): pos (W,D) | lp (W) | trial (2,B,D: the rounds alternate) | lnp_rows (2B) | X0, eta (half,D each) |
-    // Z0, L, R (half each) | T (half, MAXC) | mu[4] | mu_hist (nsteps) | block results (per) | chain segment; then the integer state
-    const size_t nd = (size_t)W * D + W + 2 * (size_t)B * D + 2 * (size_t)B + 2 * (size_t)half * D + (3 + vp::SLICE_MAXC) * (size_t)half + 4 +
-                      (size_t)std::max(nsteps, 1) + (size_t)per;                // (lnp_rows twice: rounds alternate between the two when G > 1)
-    const size_t ni = 7 * (size_t)half + 32 + seg * (size_t)W;                 // J K phase sides nshr row widx | counters, prog | perm table
-    struct Dev { double *pos, *lp, *trial, *rows, *mu, *muhist, *blk, *chain; long long* ll; int *perm, *nact, *nan, *prog; vp::SliceState st; vp::SliceCounters cn; hipStream_t s; };
+    struct Dev { double *pos, *lp, *trial, *rows, *mu, *muhist, *blk, *chain; long long* ll; int *perm, *nact, *prog; size_t zeroed; vp::SliceState st; vp::SliceCounters cn; hipStream_t s; };
     std::vector<Dev> dv(G);
     const double h_mu[4] = {*mu, *tune > 0 ? (double)(*tune - 1) : 0.0, *tune ? 1.0 : 0.0, 0.0};   // `tune` carries the state across calls
     for (int i = 0; i < G; ++i) {
         vp_ctx* ci = cx[i];
-        STRY(i, hipSetDevice(ci->device));
-        if ((rc = ensure_workspace(ci, std::max(W, B)))) { *bad = i; return rc; }
-        const size_t bytes = (nd + (i == 0 && chain ? seg * row : 0)) * sizeof(double) + 4 * sizeof(long long) + ni * sizeof(int) + 64;
-        if ((rc = ensure_scratch(ci, bytes))) { *bad = i; return rc; }
+        SLOT_TRY(F, i, hipSetDevice(ci->device));
+        if ((rc = ensure_workspace(ci, std::max(W, B)))) return F.code(i, rc);
         Dev& d = dv[i];
         d.s = ci->stream;
-        d.pos = ci->d_scratch; d.lp = d.pos + (size_t)W * D; d.trial = d.lp + W; d.rows = d.trial + 2 * (size_t)B * D;
-        d.st = vp::SliceState{};
-        d.st.X0 = d.rows + 2 * (size_t)B; d.st.eta = d.st.X0 + (size_t)half * D; d.st.Z0 = d.st.eta + (size_t)half * D;
-        d.st.L = d.st.Z0 + half; d.st.R = d.st.L + half; d.st.T = d.st.R + half;
-        d.mu = d.st.T + (size_t)half * vp::SLICE_MAXC;                        // 4 doubles (3 used)
-        d.muhist = d.mu + 4;
-        d.blk = d.muhist + std::max(nsteps, 1);
-        d.chain = d.blk + per;
-        d.ll = reinterpret_cast<long long*>(d.chain + (i == 0 && chain ? seg * row : 0));     // n_evals, nexp, ncon, (pad)
-        int* d_int = reinterpret_cast<int*>(d.ll + 4);
-        d.st.J = d_int; d.st.K = d.st.J + half; d.st.phase = d.st.K + half; d.st.sides = d.st.phase + half; d.st.nshr = d.st.sides + half;
-        d.st.row = d.st.nshr + half; d.st.widx = d.st.row + half;
-        d.nact = d.st.widx + half;                                            // n_active, nanflag, ncand, (pad)
-        d.nan = d.nact + 1;
-        d.prog = d.nact + 8;                                                  // 8 ints (slice_kernels.h SliceRun::prog)
-        d.perm = d.prog + 8;                                                  // (seg, W)
-        d.cn = vp::SliceCounters{d.nact, d.ll, d.ll + 1, d.ll + 2, d.nan, d.nact + 2, d.mu};
-        STRY(i, hipMemcpyAsync(d.pos, pos, (size_t)W * D * sizeof(double), hipMemcpyHostToDevice, d.s));
-        STRY(i, hipMemcpyAsync(d.mu, h_mu, sizeof(h_mu), hipMemcpyHostToDevice, d.s));
-        STRY(i, hipMemsetAsync(d.ll, 0, 4 * sizeof(long long), d.s));
-        STRY(i, hipMemsetAsync(d.nact, 0, 16 * sizeof(int), d.s));
-        if (have_lnprob) STRY(i, hipMemcpyAsync(d.lp, lnprob, (size_t)W * sizeof(double), hipMemcpyHostToDevice, d.s));
-        else if ((rc = enqueue_lnprob(ci, W, d.pos, d.lp, d.s))) { *bad = i; return rc; }     // (every replica: once per run)
+        if ((rc = carve_scratch(ci, [&](Arena& A) {         // every replica's state: the doubles first, then the integer state
+            d.pos = A.take<double>((size_t)W * D); d.lp = A.take<double>(W);
+            d.trial = A.take<double>(2 * (size_t)B * D); d.rows = A.take<double>(2 * (size_t)B);    // (each twice: the rounds alternate)
+            d.st.X0 = A.take<double>((size_t)half * D); d.st.eta = A.take<double>((size_t)half * D);
+            d.st.Z0 = A.take<double>(half); d.st.L = A.take<double>(half); d.st.R = A.take<double>(half);
+            d.st.T = A.take<double>((size_t)half * vp::SLICE_MAXC);
+            d.mu = A.take<double>(4); d.muhist = A.take<double>(std::max(nsteps, 1));       // (mu: 3 used)
+            d.blk = A.take<double>(per);                                // this context's block of a round's results
+            d.chain = A.take<double>(i == 0 && chain ? seg * row : 0);  // the chain segment: replica 0
+            d.ll = A.take<long long>(4);                                // n_evals, nexp, ncon, (pad)
+            d.st.J = A.take<int>(half); d.st.K = A.take<int>(half); d.st.phase = A.take<int>(half); d.st.sides = A.take<int>(half);
+            d.st.nshr = A.take<int>(half); d.st.row = A.take<int>(half); d.st.widx = A.take<int>(half);
+            // n_active, nanflag, ncand, (pad) | prog (slice_kernels.h SliceRun::prog): cleared by ONE memset
+            d.nact = A.take<int>(8); d.prog = A.take<int>(8); d.zeroed = A.bytes_from(d.nact);
+            d.perm = A.take<int>(seg * (size_t)W);                      // (seg, W)
+        }))) return F.code(i, rc);
+        d.cn = vp::SliceCounters{d.nact, d.ll, d.ll + 1, d.ll + 2, d.nact + 1, d.nact + 2, d.mu};
+        SLOT_TRY(F, i, hipMemcpyAsync(d.pos, pos, (size_t)W * D * sizeof(double), hipMemcpyHostToDevice, d.s));
+        SLOT_TRY(F, i, hipMemcpyAsync(d.mu, h_mu, sizeof(h_mu), hipMemcpyHostToDevice, d.s));
+        SLOT_TRY(F, i, hipMemsetAsync(d.ll, 0, 4 * sizeof(long long), d.s));
+        SLOT_TRY(F, i, hipMemsetAsync(d.nact, 0, d.zeroed, d.s));
+        if (have_lnprob) SLOT_TRY(F, i, hipMemcpyAsync(d.lp, lnprob, (size_t)W * sizeof(double), hipMemcpyHostToDevice, d.s));
+        else if ((rc = enqueue_lnprob(ci, W, d.pos, d.lp, d.s))) return F.code(i, rc);     // (every replica: once per run)
     }
     {   // the start state must be finite everywhere (zeus: "Invalid walker initial positions")
         std::vector<double> h_lp(W);
-        STRY(0, hipSetDevice(c->device));
-        STRY(0, hipMemcpyAsync(h_lp.data(), dv[0].lp, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, dv[0].s));
-        STRY(0, hipStreamSynchronize(dv[0].s));
+        SLOT_TRY(F, 0, hipSetDevice(c->device));
+        SLOT_TRY(F, 0, hipMemcpyAsync(h_lp.data(), dv[0].lp, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, dv[0].s));
+        SLOT_TRY(F, 0, hipStreamSynchronize(dv[0].s));
         for (int w = 0; w < W; ++w)
             if (!(std::fabs(h_lp[w]) <= 1.79e308))
-                SFAIL(0, VP_ENAN, "vp_slice_run: the initial lnprob of walker " + std::to_string(w) + " is not finite");
+                return F(0, VP_ENAN, "vp_slice_run: the initial lnprob of walker " + std::to_string(w) + " is not finite");
     }
     // two words of mapped host memory that replica 0's round kernel keeps up to date: rounds consumed, done / error
     volatile int* h_words = nullptr;
     int* d_words = nullptr;
     {
-        STRY(0, hipSetDevice(c->device));
+        SLOT_TRY(F, 0, hipSetDevice(c->device));
         if (!c->h_done) {
             if (hipHostMalloc((void**)&c->h_done, 64, hipHostMallocMapped) != hipSuccess) { c->h_done = nullptr; (void)hipGetLastError(); }
             else std::memset(c->h_done, 0, 64);
@@ -313,13 +315,13 @@ static int slice_run_impl(vp_multi* m, vp_ctx* const* cx, int G, int W, int D, d
         for (int i = 0; i < G; ++i) {
             vp_ctx* ci = cx[i];
             const Dev& d = dv[i];
-            STRY(i, hipSetDevice(ci->device));
+            SLOT_TRY(F, i, hipSetDevice(ci->device));
             if (G == 1) {
-                if ((rc = enqueue_lnprob(ci, B, d.trial + (size_t)tb * B * D, d.rows, d.s))) { *bad = i; return rc; }
+                if ((rc = enqueue_lnprob(ci, B, d.trial + (size_t)tb * B * D, d.rows, d.s))) return F.code(i, rc);
             } else {
-                const int lo = std::min(i * per, B), n = std::min(lo + per, B) - lo;
+                const auto [lo, n] = block_of(i, per, B);
                 if (n <= 0) continue;
-                if ((rc = enqueue_lnprob(ci, n, d.trial + ((size_t)tb * B + lo) * D, d.blk, d.s, B))) { *bad = i; return rc; }
+                if ((rc = enqueue_lnprob(ci, n, d.trial + ((size_t)tb * B + lo) * D, d.blk, d.s, B))) return F.code(i, rc);
                 hipLaunchKernelGGL(scatter_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, d.s, d.blk, n, lo, R);
             }
         }
@@ -331,7 +333,7 @@ static int slice_run_impl(vp_multi* m, vp_ctx* const* cx, int G, int W, int D, d
         parity ^= 1;
         tb ^= 1;
         for (int i = 0; i < G; ++i) {
-            STRY(i, hipSetDevice(cx[i]->device));
+            SLOT_TRY(F, i, hipSetDevice(cx[i]->device));
             launch_round(i, 0);
         }
         return VP_OK;
@@ -343,7 +345,7 @@ static int slice_run_impl(vp_multi* m, vp_ctx* const* cx, int G, int W, int D, d
         P.step_base = step0 + (uint64_t)done;
         if (h_words) { h_words[0] = 0; h_words[1] = 0; }
         for (int i = 0; i < G; ++i) {
-            STRY(i, hipSetDevice(cx[i]->device));
+            SLOT_TRY(F, i, hipSetDevice(cx[i]->device));
             hipLaunchKernelGGL(vp::slice_perm_kernel, dim3(n), dim3(1024), 0, dv[i].s, W, seed, P.step_base, dv[i].perm);
             launch_round(i, 1);
         }
@@ -359,10 +361,10 @@ static int slice_run_impl(vp_multi* m, vp_ctx* const* cx, int G, int W, int D, d
                     if (seen != last_seen) { last_seen = seen; t_seen = std::chrono::steady_clock::now(); idle = 0; }
                     else if (++idle > 20000) { std::this_thread::sleep_for(std::chrono::microseconds(20)); }   // (rounds of milliseconds: big models)
                     else if (std::chrono::steady_clock::now() - t_seen > std::chrono::seconds(5)) {
-                        STRY(0, hipSetDevice(c->device));
+                        SLOT_TRY(F, 0, hipSetDevice(c->device));
                         const hipError_t q = hipStreamQuery(dv[0].s);
                         if (q != hipErrorNotReady) {     // the queue ran dry (or failed) without the word moving
-                            if (q != hipSuccess) { (void)hipGetLastError(); *bad = 0; return fail(c, VP_EHIP, std::string("vp_slice_run: ") + hipGetErrorString(q)); }
+                            if (q != hipSuccess) { (void)hipGetLastError(); return F(0, VP_EHIP, std::string("vp_slice_run: ") + hipGetErrorString(q)); }
                             if (!__atomic_load_n(const_cast<int*>(h_words + 1), __ATOMIC_ACQUIRE) &&
                                 __atomic_load_n(const_cast<int*>(h_words), __ATOMIC_RELAXED) == seen) h_words = nullptr;   // word not delivered: poll by copy
                         }
@@ -375,48 +377,46 @@ static int slice_run_impl(vp_multi* m, vp_ctx* const* cx, int G, int W, int D, d
             } else {                                 // no mapped word: look at the device's state every few rounds
                 for (int r = 0; r < ahead; ++r)
                     if ((rc = round())) return rc;
-                STRY(0, hipSetDevice(c->device));
-                STRY(0, hipMemcpyAsync(h_prog, dv[0].prog, sizeof(h_prog), hipMemcpyDeviceToHost, dv[0].s));
-                STRY(0, hipStreamSynchronize(dv[0].s));
+                SLOT_TRY(F, 0, hipSetDevice(c->device));
+                SLOT_TRY(F, 0, hipMemcpyAsync(h_prog, dv[0].prog, sizeof(h_prog), hipMemcpyDeviceToHost, dv[0].s));
+                SLOT_TRY(F, 0, hipStreamSynchronize(dv[0].s));
                 if (h_prog[2]) break;
             }
         }
         // the segment is over on the device: drain what is still enqueued (launches that return at once), look at the outcome
         for (int i = G - 1; i >= 0; --i) {
-            STRY(i, hipSetDevice(cx[i]->device));
-            if (i == 0) STRY(0, hipMemcpyAsync(h_prog, dv[0].prog, sizeof(h_prog), hipMemcpyDeviceToHost, dv[0].s));
-            STRY(i, hipStreamSynchronize(dv[i].s));
+            SLOT_TRY(F, i, hipSetDevice(cx[i]->device));
+            if (i == 0) SLOT_TRY(F, 0, hipMemcpyAsync(h_prog, dv[0].prog, sizeof(h_prog), hipMemcpyDeviceToHost, dv[0].s));
+            SLOT_TRY(F, i, hipStreamSynchronize(dv[i].s));
         }
-        STRY(0, hipGetLastError());
-        if (h_prog[3] == 1) { *bad = 0; return fail(c, VP_ENAN, "vp_slice_run: Log Probability returned NaN"); }
-        if (h_prog[3]) { *bad = 0; return fail(c, VP_ESTATE, "vp_slice_run: a slice did not terminate"); }
+        SLOT_TRY(F, 0, hipGetLastError());
+        if (h_prog[3] == 1) return F(0, VP_ENAN, "vp_slice_run: Log Probability returned NaN");
+        if (h_prog[3]) return F(0, VP_ESTATE, "vp_slice_run: a slice did not terminate");
         if (chain) {
-            STRY(0, hipMemcpyAsync(chain + (size_t)done * W * D, dv[0].chain, (size_t)n * W * D * sizeof(double), hipMemcpyDeviceToHost, dv[0].s));
-            STRY(0, hipMemcpyAsync(chain_lnprob + (size_t)done * W, dv[0].chain + seg * (size_t)W * D, (size_t)n * W * sizeof(double),
-                                   hipMemcpyDeviceToHost, dv[0].s));
-            STRY(0, hipStreamSynchronize(dv[0].s));
+            SLOT_TRY(F, 0, hipMemcpyAsync(chain + (size_t)done * W * D, dv[0].chain, (size_t)n * W * D * sizeof(double), hipMemcpyDeviceToHost, dv[0].s));
+            SLOT_TRY(F, 0, hipMemcpyAsync(chain_lnprob + (size_t)done * W, dv[0].chain + seg * (size_t)W * D, (size_t)n * W * sizeof(double),
+                                         hipMemcpyDeviceToHost, dv[0].s));
+            SLOT_TRY(F, 0, hipStreamSynchronize(dv[0].s));
         }
         if (G > 1 && (rc = multi_barrier(m))) return rc;
         done += n;
     }
-    STRY(0, hipSetDevice(c->device));
+    SLOT_TRY(F, 0, hipSetDevice(c->device));
     double h_mu_out[4];
     long long h_ll[4];
-    STRY(0, hipMemcpyAsync(pos, dv[0].pos, (size_t)W * D * sizeof(double), hipMemcpyDeviceToHost, dv[0].s));
-    STRY(0, hipMemcpyAsync(lnprob, dv[0].lp, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, dv[0].s));
-    STRY(0, hipMemcpyAsync(h_mu_out, dv[0].mu, sizeof(h_mu_out), hipMemcpyDeviceToHost, dv[0].s));
-    STRY(0, hipMemcpyAsync(h_ll, dv[0].ll, sizeof(h_ll), hipMemcpyDeviceToHost, dv[0].s));
-    if (mu_history && nsteps > 0) STRY(0, hipMemcpyAsync(mu_history, dv[0].muhist, (size_t)nsteps * sizeof(double), hipMemcpyDeviceToHost, dv[0].s));
-    STRY(0, hipStreamSynchronize(dv[0].s));
+    SLOT_TRY(F, 0, hipMemcpyAsync(pos, dv[0].pos, (size_t)W * D * sizeof(double), hipMemcpyDeviceToHost, dv[0].s));
+    SLOT_TRY(F, 0, hipMemcpyAsync(lnprob, dv[0].lp, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, dv[0].s));
+    SLOT_TRY(F, 0, hipMemcpyAsync(h_mu_out, dv[0].mu, sizeof(h_mu_out), hipMemcpyDeviceToHost, dv[0].s));
+    SLOT_TRY(F, 0, hipMemcpyAsync(h_ll, dv[0].ll, sizeof(h_ll), hipMemcpyDeviceToHost, dv[0].s));
+    if (mu_history && nsteps > 0) SLOT_TRY(F, 0, hipMemcpyAsync(mu_history, dv[0].muhist, (size_t)nsteps * sizeof(double), hipMemcpyDeviceToHost, dv[0].s));
+    SLOT_TRY(F, 0, hipStreamSynchronize(dv[0].s));
     for (int i = 1; i < G; ++i) {                                    // the other replicas have nothing left in flight either
-        STRY(i, hipSetDevice(cx[i]->device));
-        STRY(i, hipStreamSynchronize(dv[i].s));
+        SLOT_TRY(F, i, hipSetDevice(cx[i]->device));
+        SLOT_TRY(F, i, hipStreamSynchronize(dv[i].s));
     }
     *mu = h_mu_out[0];
     *tune = h_mu_out[2] != 0.0 ? 1 + (int)h_mu_out[1] : 0;
     if (n_evals) *n_evals += (int64_t)h_ll[0];
-#undef STRY
-#undef SFAIL
     return VP_OK;
 }
 

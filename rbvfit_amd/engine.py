@@ -31,26 +31,45 @@ def device_count() -> int:
     return int(L.load().vp_device_count())
 
 
-class Engine:
-    """Context on one GPU.  Not fork-safe: the creating pid is recorded and any use from another
-    process raises (rbvfit's default ``use_pool=True`` forks; pass ``use_pool=False``)."""
+def _ensemble_buffers(pos, nsteps, lnprob, store_chain):
+    """What both device samplers take and give back: (pos (W, D), lnprob (W,), was lnprob given?, chain, chain_lnprob), the
+    first two copies the run updates in place, the chain arrays None unless ``store_chain``."""
+    pos = np.array(pos, dtype=np.float64, order="C")
+    if pos.ndim != 2:
+        raise ValueError("pos must have shape (nwalkers, ndim)")
+    W, D = pos.shape
+    have = lnprob is not None
+    lp = np.array(lnprob, dtype=np.float64) if have else np.empty(W, dtype=np.float64)
+    if lp.shape != (W,):
+        raise ValueError("lnprob must have shape (nwalkers,)")
+    chain = np.empty((nsteps, W, D), dtype=np.float64) if store_chain else None
+    clp = np.empty((nsteps, W), dtype=np.float64) if store_chain else None
+    return pos, lp, have, chain, clp
 
-    def __init__(self, device_id: int = 0):
+
+class _Handle:
+    """What ``Engine`` (a ``vp_ctx``) and ``MultiEngine`` (a ``vp_multi``) have in common: the C handle ``_ctx`` with its lifetime,
+    fork guard and error check, and the marshalling of the entry points both kinds of handle have (``_C`` names them)."""
+    _C: dict = {}
+    _NAME = _FORK_HINT = ""
+
+    def _open(self, *args):
         self._lib = L.load()
         self._ctx = C.c_void_p()
-        rc = self._lib.vp_ctx_create(C.byref(self._ctx), int(device_id))
+        rc = self._fn("create")(C.byref(self._ctx), *args)
         if rc != L.VP_OK:
-            msg = self._lib.vp_last_error(None)
-            raise L.RbvfitAmdError(rc, msg.decode() if msg else "vp_ctx_create failed")
+            msg = self._fn("last_error")(None)
+            raise L.RbvfitAmdError(rc, msg.decode() if msg else self._C["create"] + " failed")
         self._pid = os.getpid()
-        self.device_id = int(device_id)
         self.ndim = 0
-        self.n_pixels = []
+
+    def _fn(self, what):
+        return getattr(self._lib, self._C[what])
 
     # -- lifetime ---------------------------------------------------------------------------
     def close(self):
         if getattr(self, "_ctx", None) and self._ctx.value and os.getpid() == self._pid:
-            self._lib.vp_ctx_destroy(self._ctx)
+            self._fn("destroy")(self._ctx)
         self._ctx = C.c_void_p()
 
     def __del__(self):
@@ -67,27 +86,22 @@ class Engine:
 
     def _guard(self):
         if os.getpid() != self._pid:
-            raise RuntimeError("rbvfit_amd.Engine used in a forked child: a HIP context does not survive "
-                               "fork(); create the engine in the process that uses it (use_pool=False)")
+            raise RuntimeError(f"rbvfit_amd.{self._NAME} used in a forked child{self._FORK_HINT}")
         if not self._ctx.value:
-            raise RuntimeError("rbvfit_amd.Engine is closed")
+            raise RuntimeError(f"rbvfit_amd.{self._NAME} is closed")
 
     def _check(self, rc):
-        L.check(self._lib, self._ctx, rc)
+        if rc != L.VP_OK:
+            msg = self._fn("last_error")(self._ctx)
+            raise L.RbvfitAmdError(rc, msg.decode() if msg else "unknown error")
 
     # -- setup ------------------------------------------------------------------------------
-    def set_option(self, name: str, value: int):
-        """Tuning knob of this context (``vp_set_option``): "geom", "finalize", "walker", ...; the
-        RBVFIT_AMD_<NAME> environment variables only give the defaults, read when the context is made."""
-        self._guard()
-        self._check(self._lib.vp_set_option(self._ctx, str(name).encode(), int(value)))
-
     def set_bounds(self, lb, ub):
         self._guard()
         lb, ub = _f64(lb).ravel(), _f64(ub).ravel()
         if lb.shape != ub.shape:
             raise ValueError("lb and ub must have the same length")
-        self._check(self._lib.vp_set_bounds(self._ctx, lb.size, _dp(lb), _dp(ub)))
+        self._check(self._fn("set_bounds")(self._ctx, lb.size, _dp(lb), _dp(ub)))
         self.ndim = lb.size
 
     def add_instrument(self, wave, flux, inv_sigma2, log_inv_sigma2, lambda0, gamma, f, zfac,
@@ -108,19 +122,14 @@ class Engine:
             t = _f64(taps)
             K, tp = t.size, _dp(t)
         idx = C.c_int(-1)
-        self._check(self._lib.vp_add_instrument(
+        self._check(self._fn("add_instrument")(
             self._ctx, wave.size, _dp(wave), _dp(flux), _dp(w), _dp(lw), lam.size, _dp(lam), _dp(gam),
             _dp(fo), _dp(zf), _ip(ni), _ip(bi), _ip(vi), K, tp, int(lsf_mode), int(voigt_method), C.byref(idx)))
-        self.n_pixels.append(wave.size)
+        self._instrument_added(wave.size)
         return idx.value
 
-    def update_spectrum(self, inst, flux, inv_sigma2, log_inv_sigma2):
-        self._guard()
-        fl, w, lw = _f64(flux), _f64(inv_sigma2), _f64(log_inv_sigma2)
-        P = self.n_pixels[inst]
-        if not (fl.shape == w.shape == lw.shape == (P,)):
-            raise ValueError(f"arrays must have shape ({P},)")
-        self._check(self._lib.vp_update_spectrum(self._ctx, int(inst), _dp(fl), _dp(w), _dp(lw)))
+    def _instrument_added(self, n_pixels):
+        pass
 
     # -- evaluation -------------------------------------------------------------------------
     def _theta2d(self, theta):
@@ -131,6 +140,72 @@ class Engine:
             raise ValueError(f"theta must have shape (W, {self.ndim}) or ({self.ndim},); got {np.shape(theta)}")
         return th
 
+    # -- device-resident ensemble samplers ----------------------------------------------------
+    def _stretch_run(self, pos, nsteps, lnprob, a, seed, step0, store_chain, naccepted):
+        self._guard()
+        pos, lp, have, chain, clp = _ensemble_buffers(pos, nsteps, lnprob, store_chain)
+        W, D = pos.shape
+        nacc = np.zeros(W, dtype=np.int64) if naccepted is None else np.ascontiguousarray(naccepted, dtype=np.int64)
+        rc = self._fn("stretch_run")(self._ctx, W, D, _dp(pos), _dp(lp), 1 if have else 0, int(nsteps), float(a),
+                                     C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint64(int(step0)),
+                                     _dp(chain) if store_chain else None, _dp(clp) if store_chain else None,
+                                     nacc.ctypes.data_as(C.POINTER(C.c_int64)))
+        if rc == L.VP_ENAN:
+            raise ValueError("Probability function returned NaN")
+        self._check(rc)
+        return pos, lp, chain, clp, nacc
+
+    def _slice_run(self, pos, nsteps, lnprob, mu, tune, tolerance, patience, maxsteps, seed, step0, store_chain):
+        self._guard()
+        pos, lp, have, chain, clp = _ensemble_buffers(pos, nsteps, lnprob, store_chain)
+        W, D = pos.shape
+        hist = np.empty(max(nsteps, 1), dtype=np.float64)
+        # tune: False / True, or the integer state a previous call returned in "tune_state" (1 + consecutive in-tolerance iterations)
+        c_mu, c_tune, c_ne = C.c_double(float(mu)), C.c_int(int(tune) if tune else 0), C.c_int64(0)
+        rc = self._fn("slice_run")(self._ctx, W, D, _dp(pos), _dp(lp), 1 if have else 0, int(nsteps), C.byref(c_mu),
+                                   C.byref(c_tune), float(tolerance), int(patience), int(maxsteps),
+                                   C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint64(int(step0)),
+                                   _dp(chain) if store_chain else None, _dp(clp) if store_chain else None, _dp(hist),
+                                   C.byref(c_ne))
+        if rc == L.VP_ENAN:
+            msg = self._fn("last_error")(self._ctx)
+            raise ValueError(msg.decode() if msg else "Log Probability returned NaN")
+        self._check(rc)
+        return dict(pos=pos, lnprob=lp, chain=chain, chain_lnprob=clp, mu=c_mu.value, tune=bool(c_tune.value),
+                    tune_state=int(c_tune.value), mu_history=hist[:nsteps], n_evals=int(c_ne.value))
+
+
+class Engine(_Handle):
+    """Context on one GPU.  Not fork-safe: the creating pid is recorded and any use from another
+    process raises (rbvfit's default ``use_pool=True`` forks; pass ``use_pool=False``)."""
+    _C = dict(create="vp_ctx_create", destroy="vp_ctx_destroy", last_error="vp_last_error", set_bounds="vp_set_bounds",
+              add_instrument="vp_add_instrument", stretch_run="vp_stretch_run", slice_run="vp_slice_run")
+    _NAME = "Engine"
+    _FORK_HINT = ": a HIP context does not survive fork(); create the engine in the process that uses it (use_pool=False)"
+
+    def __init__(self, device_id: int = 0):
+        self._open(int(device_id))
+        self.device_id = int(device_id)
+        self.n_pixels = []
+
+    def _instrument_added(self, n_pixels):
+        self.n_pixels.append(n_pixels)
+
+    def set_option(self, name: str, value: int):
+        """Tuning knob of this context (``vp_set_option``): "geom", "finalize", "walker", ...; the
+        RBVFIT_AMD_<NAME> environment variables only give the defaults, read when the context is made."""
+        self._guard()
+        self._check(self._lib.vp_set_option(self._ctx, str(name).encode(), int(value)))
+
+    def update_spectrum(self, inst, flux, inv_sigma2, log_inv_sigma2):
+        self._guard()
+        fl, w, lw = _f64(flux), _f64(inv_sigma2), _f64(log_inv_sigma2)
+        P = self.n_pixels[inst]
+        if not (fl.shape == w.shape == lw.shape == (P,)):
+            raise ValueError(f"arrays must have shape ({P},)")
+        self._check(self._lib.vp_update_spectrum(self._ctx, int(inst), _dp(fl), _dp(w), _dp(lw)))
+
+    # -- evaluation -------------------------------------------------------------------------
     def lnprob(self, theta) -> np.ndarray:
         """(W, D) host array -> (W,) lnprob (H2D, kernels, D2H inside the call).
 
@@ -330,26 +405,7 @@ class Engine:
         accept/reject stay in HBM).  Returns (pos, lnprob, chain, chain_lnprob, naccepted);
         chain arrays are None when ``store_chain`` is False.  Raises ValueError when a proposal's
         lnprob is NaN, as emcee does."""
-        self._guard()
-        pos = np.array(pos, dtype=np.float64, order="C")
-        if pos.ndim != 2:
-            raise ValueError("pos must have shape (nwalkers, ndim)")
-        W, D = pos.shape
-        have = lnprob is not None
-        lp = np.array(lnprob, dtype=np.float64) if have else np.empty(W, dtype=np.float64)
-        if lp.shape != (W,):
-            raise ValueError("lnprob must have shape (nwalkers,)")
-        chain = np.empty((nsteps, W, D), dtype=np.float64) if store_chain else None
-        clp = np.empty((nsteps, W), dtype=np.float64) if store_chain else None
-        nacc = np.zeros(W, dtype=np.int64) if naccepted is None else np.ascontiguousarray(naccepted, dtype=np.int64)
-        rc = self._lib.vp_stretch_run(self._ctx, W, D, _dp(pos), _dp(lp), 1 if have else 0, int(nsteps), float(a),
-                                      C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint64(int(step0)),
-                                      _dp(chain) if store_chain else None, _dp(clp) if store_chain else None,
-                                      nacc.ctypes.data_as(C.POINTER(C.c_int64)))
-        if rc == L.VP_ENAN:
-            raise ValueError("Probability function returned NaN")
-        self._check(rc)
-        return pos, lp, chain, clp, nacc
+        return self._stretch_run(pos, nsteps, lnprob, a, seed, step0, store_chain, naccepted)
 
     # -- device-resident ensemble slice sampler (vp_slice_run) ------------------------------------
     def slice_run(self, pos, nsteps: int, lnprob=None, mu: float = 1.0, tune: bool = True, tolerance: float = 0.05,
@@ -358,31 +414,7 @@ class Engine:
         active sets of the stepping-out / shrinking rounds are compacted in HBM.  Returns a dict: pos, lnprob,
         chain, chain_lnprob (None when ``store_chain`` is False), mu, tune (still adapting?), tune_state (pass it back as
         ``tune`` to continue the run: the patience counter travels with it), mu_history, n_evals."""
-        self._guard()
-        pos = np.array(pos, dtype=np.float64, order="C")
-        if pos.ndim != 2:
-            raise ValueError("pos must have shape (nwalkers, ndim)")
-        W, D = pos.shape
-        have = lnprob is not None
-        lp = np.array(lnprob, dtype=np.float64) if have else np.empty(W, dtype=np.float64)
-        if lp.shape != (W,):
-            raise ValueError("lnprob must have shape (nwalkers,)")
-        chain = np.empty((nsteps, W, D), dtype=np.float64) if store_chain else None
-        clp = np.empty((nsteps, W), dtype=np.float64) if store_chain else None
-        hist = np.empty(max(nsteps, 1), dtype=np.float64)
-        # tune: False / True, or the integer state a previous call returned in "tune_state" (1 + consecutive in-tolerance iterations)
-        c_mu, c_tune, c_ne = C.c_double(float(mu)), C.c_int(int(tune) if tune else 0), C.c_int64(0)
-        rc = self._lib.vp_slice_run(self._ctx, W, D, _dp(pos), _dp(lp), 1 if have else 0, int(nsteps), C.byref(c_mu),
-                                    C.byref(c_tune), float(tolerance), int(patience), int(maxsteps),
-                                    C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint64(int(step0)),
-                                    _dp(chain) if store_chain else None, _dp(clp) if store_chain else None, _dp(hist),
-                                    C.byref(c_ne))
-        if rc == L.VP_ENAN:
-            msg = self._lib.vp_last_error(self._ctx)
-            raise ValueError(msg.decode() if msg else "Log Probability returned NaN")
-        self._check(rc)
-        return dict(pos=pos, lnprob=lp, chain=chain, chain_lnprob=clp, mu=c_mu.value, tune=bool(c_tune.value),
-                    tune_state=int(c_tune.value), mu_history=hist[:nsteps], n_evals=int(c_ne.value))
+        return self._slice_run(pos, nsteps, lnprob, mu, tune, tolerance, patience, maxsteps, seed, step0, store_chain)
 
     @property
     def last_launch_kind(self) -> str:
@@ -433,52 +465,22 @@ class Engine:
         return dict(prep_ms=a.value, tile_ms=b.value, finalize_ms=c_.value, n_tile_launches=n.value)
 
 
-class MultiEngine:
+class MultiEngine(_Handle):
     """Several GPUs from ONE process through ``vp_multi_*`` (no torch, no RCCL): one context per entry of
     ``device_ids`` (a device may appear more than once), identical static data on each, and ``lnprob``
     shards the walker rows in contiguous blocks of ceil(W / n) -- ``rbvfit_amd.dist.shard_bounds`` --
     with every block in flight before any is waited for.  The torch-free counterpart of
     ``rbvfit_amd.dist.ShardedPosterior`` (which is one process per GPU + an RCCL all-gather)."""
 
+    _C = dict(create="vp_multi_create", destroy="vp_multi_destroy", last_error="vp_multi_last_error", set_bounds="vp_multi_set_bounds",
+              add_instrument="vp_multi_add_instrument", stretch_run="vp_multi_stretch_run", slice_run="vp_multi_slice_run")
+    _NAME = "MultiEngine"
+    _FORK_HINT = " (a HIP context does not survive fork())"
+    _m = property(lambda self: self._ctx)         # the vp_multi handle
+
     def __init__(self, device_ids: Sequence[int]):
-        self._lib = L.load()
-        self._m = C.c_void_p()
-        ids = (C.c_int * len(device_ids))(*[int(d) for d in device_ids])
-        rc = self._lib.vp_multi_create(C.byref(self._m), len(device_ids), ids)
-        if rc != L.VP_OK:
-            msg = self._lib.vp_multi_last_error(None)
-            raise L.RbvfitAmdError(rc, msg.decode() if msg else "vp_multi_create failed")
-        self._pid = os.getpid()
+        self._open(len(device_ids), (C.c_int * len(device_ids))(*[int(d) for d in device_ids]))
         self.device_ids = [int(d) for d in device_ids]
-        self.ndim = 0
-
-    def close(self):
-        if getattr(self, "_m", None) and self._m.value and os.getpid() == self._pid:
-            self._lib.vp_multi_destroy(self._m)
-        self._m = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _guard(self):
-        if os.getpid() != self._pid:
-            raise RuntimeError("rbvfit_amd.MultiEngine used in a forked child (a HIP context does not survive fork())")
-        if not self._m.value:
-            raise RuntimeError("rbvfit_amd.MultiEngine is closed")
-
-    def _check(self, rc):
-        if rc != L.VP_OK:
-            msg = self._lib.vp_multi_last_error(self._m)
-            raise L.RbvfitAmdError(rc, msg.decode() if msg else "unknown error")
 
     @property
     def n_devices(self) -> int:
@@ -490,42 +492,9 @@ class MultiEngine:
             ctx = C.c_void_p(self._lib.vp_multi_ctx(self._m, i))
             L.check(self._lib, ctx, self._lib.vp_set_option(ctx, str(name).encode(), int(value)))
 
-    def set_bounds(self, lb, ub):
-        self._guard()
-        lb, ub = _f64(lb).ravel(), _f64(ub).ravel()
-        if lb.shape != ub.shape:
-            raise ValueError("lb and ub must have the same length")
-        self._check(self._lib.vp_multi_set_bounds(self._m, lb.size, _dp(lb), _dp(ub)))
-        self.ndim = lb.size
-
-    def add_instrument(self, wave, flux, inv_sigma2, log_inv_sigma2, lambda0, gamma, f, zfac,
-                       N_idx, b_idx, v_idx, taps=None, lsf_mode=L.LSF_NONE, voigt_method=L.VOIGT_WOFZ) -> int:
-        self._guard()
-        wave, flux, w, lw = _f64(wave), _f64(flux), _f64(inv_sigma2), _f64(log_inv_sigma2)
-        if not (wave.ndim == 1 and wave.shape == flux.shape == w.shape == lw.shape):
-            raise ValueError("wave, flux, inv_sigma2 and log_inv_sigma2 must be 1-D arrays of equal length")
-        lam, gam, fo, zf = _f64(lambda0), _f64(gamma), _f64(f), _f64(zfac)
-        ni = np.ascontiguousarray(N_idx, dtype=np.int32)
-        bi = np.ascontiguousarray(b_idx, dtype=np.int32)
-        vi = np.ascontiguousarray(v_idx, dtype=np.int32)
-        if taps is None or lsf_mode == L.LSF_NONE or len(taps) == 0:
-            K, tp, lsf_mode = 0, None, L.LSF_NONE
-        else:
-            t = _f64(taps)
-            K, tp = t.size, _dp(t)
-        idx = C.c_int(-1)
-        self._check(self._lib.vp_multi_add_instrument(
-            self._m, wave.size, _dp(wave), _dp(flux), _dp(w), _dp(lw), lam.size, _dp(lam), _dp(gam),
-            _dp(fo), _dp(zf), _ip(ni), _ip(bi), _ip(vi), K, tp, int(lsf_mode), int(voigt_method), C.byref(idx)))
-        return idx.value
-
     def lnprob(self, theta) -> np.ndarray:
         self._guard()
-        th = _f64(theta)
-        if th.ndim == 1:
-            th = th[None, :]
-        if th.ndim != 2 or th.shape[1] != self.ndim:
-            raise ValueError(f"theta must have shape (W, {self.ndim}) or ({self.ndim},); got {np.shape(theta)}")
+        th = self._theta2d(theta)
         out = np.empty(th.shape[0], dtype=np.float64)
         self._check(self._lib.vp_multi_lnprob_batch(self._m, th.shape[0], th.shape[1], _dp(th), _dp(out)))
         return out
@@ -536,53 +505,11 @@ class MultiEngine:
         every context keeps the whole ensemble in HBM and runs its block of each half-step; moved rows are written into
         every replica, half-steps are ordered by events.  Same arguments and results -- the same chain, bit for bit,
         whatever the number of contexts."""
-        self._guard()
-        pos = np.array(pos, dtype=np.float64, order="C")
-        if pos.ndim != 2:
-            raise ValueError("pos must have shape (nwalkers, ndim)")
-        W, D = pos.shape
-        have = lnprob is not None
-        lp = np.array(lnprob, dtype=np.float64) if have else np.empty(W, dtype=np.float64)
-        if lp.shape != (W,):
-            raise ValueError("lnprob must have shape (nwalkers,)")
-        chain = np.empty((nsteps, W, D), dtype=np.float64) if store_chain else None
-        clp = np.empty((nsteps, W), dtype=np.float64) if store_chain else None
-        nacc = np.zeros(W, dtype=np.int64) if naccepted is None else np.ascontiguousarray(naccepted, dtype=np.int64)
-        rc = self._lib.vp_multi_stretch_run(self._m, W, D, _dp(pos), _dp(lp), 1 if have else 0, int(nsteps), float(a),
-                                            C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint64(int(step0)),
-                                            _dp(chain) if store_chain else None, _dp(clp) if store_chain else None,
-                                            nacc.ctypes.data_as(C.POINTER(C.c_int64)))
-        if rc == L.VP_ENAN:
-            raise ValueError("Probability function returned NaN")
-        self._check(rc)
-        return pos, lp, chain, clp, nacc
+        return self._stretch_run(pos, nsteps, lnprob, a, seed, step0, store_chain, naccepted)
 
     def slice_run(self, pos, nsteps: int, lnprob=None, mu: float = 1.0, tune=True, tolerance: float = 0.05,
                   patience: int = 5, maxsteps: int = 10000, seed: int = 0, step0: int = 0, store_chain: bool = True):
         """``Engine.slice_run`` for ONE ensemble on this object's device contexts (``vp_multi_slice_run``): the sampler
         state is replicated, every round's lnprob batch is cut into one block of trial rows per context.  Same arguments
         and results -- the same chain, bit for bit, whatever the number of contexts."""
-        self._guard()
-        pos = np.array(pos, dtype=np.float64, order="C")
-        if pos.ndim != 2:
-            raise ValueError("pos must have shape (nwalkers, ndim)")
-        W, D = pos.shape
-        have = lnprob is not None
-        lp = np.array(lnprob, dtype=np.float64) if have else np.empty(W, dtype=np.float64)
-        if lp.shape != (W,):
-            raise ValueError("lnprob must have shape (nwalkers,)")
-        chain = np.empty((nsteps, W, D), dtype=np.float64) if store_chain else None
-        clp = np.empty((nsteps, W), dtype=np.float64) if store_chain else None
-        hist = np.empty(max(nsteps, 1), dtype=np.float64)
-        c_mu, c_tune, c_ne = C.c_double(float(mu)), C.c_int(int(tune) if tune else 0), C.c_int64(0)
-        rc = self._lib.vp_multi_slice_run(self._m, W, D, _dp(pos), _dp(lp), 1 if have else 0, int(nsteps), C.byref(c_mu),
-                                          C.byref(c_tune), float(tolerance), int(patience), int(maxsteps),
-                                          C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint64(int(step0)),
-                                          _dp(chain) if store_chain else None, _dp(clp) if store_chain else None, _dp(hist),
-                                          C.byref(c_ne))
-        if rc == L.VP_ENAN:
-            msg = self._lib.vp_multi_last_error(self._m)
-            raise ValueError(msg.decode() if msg else "Log Probability returned NaN")
-        self._check(rc)
-        return dict(pos=pos, lnprob=lp, chain=chain, chain_lnprob=clp, mu=c_mu.value, tune=bool(c_tune.value),
-                    tune_state=int(c_tune.value), mu_history=hist[:nsteps], n_evals=int(c_ne.value))
+        return self._slice_run(pos, nsteps, lnprob, mu, tune, tolerance, patience, maxsteps, seed, step0, store_chain)
