@@ -197,8 +197,16 @@ int vp_lnprob_grad_batch_device(vp_ctx* ctx, int W, int D, const double* d_theta
                                 void* hip_stream);
 
 /* w(x_j + i a_i) = H + i L on the device for a grid (host buffers; H and L are row-major (na, nx)).  Test hook, like
- * vp_voigt_h, for the complex tiers of the gradient kernels (tier chosen per wavefront = 64 consecutive x_j of one a_i). */
+ * vp_voigt_h, for the complex tiers the gradient kernels form their derivatives from: the core series (|x| < 8, 0 <= a <= 0.1) and
+ * the evaluation outside the fast domain (a > 0.1, a < 0).  Its series for |x| >= 8, 0 <= a <= 0.1 are this hook's own: the
+ * gradient kernels sum the series of the derivatives there, which vp_voigt_dw shows.  Tier chosen per wavefront = 64
+ * consecutive x_j of one a_i. */
 int vp_voigt_w(vp_ctx* ctx, int na, const double* a, int nx, const double* x, double* H, double* L);
+
+/* H = Re w, Hx = Re w' and G = Re (z w)' at z = x_j + i a_i (host buffers; row-major (na, nx)): the three quantities the gradient
+ * kernels build d tau / d logN, d tau / d v and d tau / d b from, through the very device function those kernels call, with the
+ * mode and term count a line of damping a_i carries.  Test hook; tier chosen per wavefront = 64 consecutive x_j of one a_i. */
+int vp_voigt_dw(vp_ctx* ctx, int na, const double* a, int nx, const double* x, double* H, double* Hx, double* G);
 
 /* H(a_i, x_j) = Re w(x_j + i a_i) on the device for a grid (host buffers; out is row-major
  * (na, nx)).  Test hook for the Faddeeva tiers that replace scipy.special.wofz at the call site

@@ -59,6 +59,7 @@ SIGNATURES = {
     "vp_lnprob_grad_batch": (C.c_int, [_ctx, C.c_int, C.c_int, _dp, _dp, _dp]),
     "vp_lnprob_grad_batch_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vp_voigt_w": (C.c_int, [_ctx, C.c_int, _dp, C.c_int, _dp, _dp, _dp]),
+    "vp_voigt_dw": (C.c_int, [_ctx, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "vp_voigt_h": (C.c_int, [_ctx, C.c_int, _dp, C.c_int, _dp, _dp]),
     "vp_stretch_run": (C.c_int, [_ctx, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_uint64,
                                  _dp, _dp, C.POINTER(C.c_int64)]),

@@ -11,7 +11,7 @@
 //   capi_samplers.inc     vp_stretch_run, vp_slice_run
 //   capi_multi.inc        vp_multi_* (several device contexts, one process)
 //   capi_misc.inc         test hooks, timing, introspection
-//   capi_grad.inc         vp_lnprob_grad_batch* (analytic gradient, grad_kernels.h), vp_voigt_w
+//   capi_grad.inc         vp_lnprob_grad_batch* (analytic gradient, grad_kernels.h), vp_voigt_w, vp_voigt_dw
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

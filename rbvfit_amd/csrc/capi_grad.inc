@@ -1,4 +1,4 @@
-// capi_grad.inc -- entry points: lnprob with its analytic gradient (grad_kernels.h), the w(z) test hook.
+// capi_grad.inc -- entry points: lnprob with its analytic gradient (grad_kernels.h), the test hooks for w(z) and its derivatives.
 // A fragment of the ONE translation unit capi.hip (included there inside extern "C", in order; not a header of its own).
 namespace {
 
@@ -137,6 +137,31 @@ int vp_voigt_w(vp_ctx* c, int na, const double* a, int nx, const double* x, doub
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(H, d_H, no * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(L, d_L, no * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return VP_OK;
+}
+
+int vp_voigt_dw(vp_ctx* c, int na, const double* a, int nx, const double* x, double* H, double* Hx, double* G) {
+    if (!c) return VP_EINVAL;
+    CtxGuard g(c);
+    if (na <= 0 || nx <= 0 || !a || !x || !H || !Hx || !G) return fail(c, VP_EINVAL, "vp_voigt_dw: empty or NULL input");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t no = (size_t)na * nx;
+    int rc;
+    if ((rc = ensure_scratch(c, (na + nx + 3 * no) * sizeof(double)))) return rc;
+    double* d_a = c->d_scratch;
+    double* d_x = d_a + na;
+    double* d_H = d_x + nx;
+    double* d_Hx = d_H + no;
+    double* d_G = d_Hx + no;
+    HIP_TRY(c, hipMemcpyAsync(d_a, a, na * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_x, x, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(vp::voigt_dw_kernel, dim3((nx + vp::GRAD_THREADS - 1) / vp::GRAD_THREADS, na), dim3(vp::GRAD_THREADS), 0, c->stream,
+                       d_a, d_x, nx, d_H, d_Hx, d_G);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(H, d_H, no * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(Hx, d_Hx, no * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(G, d_G, no * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return VP_OK;
 }

@@ -132,7 +132,7 @@ __global__ __launch_bounds__(GRAD_THREADS) void grad_lines_kernel(InstDev I, con
         const int p = p0 + (int)threadIdx.x;
         const int pc = min(p, I.P - 1);
         const double x = faithful_x(I.wave[pc], I.ginv[pc], r);
-        const DW h = (mode == 0) ? dw_fast(x, a, ea2, nodd) : dw_from_w(x, a, w_generic(x, a));
+        const DW h = dw_line(x, a, ea2, mode, nodd);
         const double sp = p < I.P ? sw[p] : 0.0;
         const double dN = LN10 * (T * h.H);
         const double dB = -(T * ib) * h.G;
@@ -175,7 +175,9 @@ __global__ __launch_bounds__(GRAD_THREADS) void grad_reduce_kernel(LinesDev T, c
     grad[idx] += acc;
 }
 
-// Test hook: w(x_j + i a_i) with the tier logic of the gradient kernels (wave = 64 consecutive x_j of one a_i).
+// Test hook: w(x_j + i a_i), H and L (wave = 64 consecutive x_j of one a_i).  What dw_from_w consumes in the core (w_core_taylor)
+// and outside the fast domain (w_generic); for 0 <= a <= 0.1 and |x| >= 8 the series are w_fast's own (voigt_dw_kernel shows
+// what the gradient takes there).
 __global__ __launch_bounds__(GRAD_THREADS) void voigt_w_kernel(const double* __restrict__ a, const double* __restrict__ x, int nx,
                                                                double* __restrict__ H, double* __restrict__ L) {
     const double ai = a[blockIdx.y];
@@ -186,6 +188,22 @@ __global__ __launch_bounds__(GRAD_THREADS) void voigt_w_kernel(const double* __r
     if (j < nx) {
         H[(size_t)blockIdx.y * nx + j] = h.H;
         L[(size_t)blockIdx.y * nx + j] = h.L;
+    }
+}
+
+// Test hook: H, Hx = Re w', G = Re (z w)' at (x_j, a_i) through dw_line, the function grad_lines_kernel calls, with the mode and
+// the term count a line record of that a would carry (wave = 64 consecutive x_j of one a_i).
+__global__ __launch_bounds__(GRAD_THREADS) void voigt_dw_kernel(const double* __restrict__ a, const double* __restrict__ x, int nx,
+                                                                double* __restrict__ H, double* __restrict__ Hx, double* __restrict__ G) {
+    const double ai = a[blockIdx.y];
+    const int j = blockIdx.x * GRAD_THREADS + threadIdx.x;
+    const double xj = x[min(j, nx - 1)];                  // (every lane stays active: the tiers are chosen by ballot)
+    const DW h = dw_line(xj, ai, ea2_small(ai), dw_mode(ai), core_terms(ai));
+    if (j < nx) {
+        const size_t at = (size_t)blockIdx.y * nx + j;
+        H[at] = h.H;
+        Hx[at] = h.Hx;
+        G[at] = h.G;
     }
 }
 

@@ -211,7 +211,43 @@ __device__ __forceinline__ DW dw_fast(double x, double a, double ea2, int nodd) 
     return d;
 }
 
-// Fast domain (0 <= a <= 0.1), tier by wavefront like line_tau_wofz: every lane of the wave must be active.
+// Outside the fast domain (a > 0.1, a < 0): per-lane branches, slow, rare.  H and L of w_generic are good to 1e-13 |H|, but Hx and G
+// formed from them lose |z|^2 and |z|^4 ulp at every x once a is large (a line with a > 0.1 has b << 1 km/s: nearly all of its
+// pixels lie at |x| >> 100, where G from H and L is noise).  So from |z| = 7 on the series of w' and (z w)' are summed directly,
+// as in the fast domain: the series in 1/z^2 does not care how large a is; 24 terms leave 4e-14 of G at |z| = 7.2 and 1e-13 at 7
+// (against the 40-digit grid, tests/golden/wgrid/dwgrid.npz).  Below |z| = 7 (a < 7 there) H and L come from the Gaussian sum
+// also for 6 <= |x| < 7, where its 26 terms still hold (3e-15 |H|): the continued fraction w_generic takes from |x| = 6 is 1e-13 |H|
+// off at small a, which the rule multiplies by 2 x^4 / 3 in G.
+constexpr int NWING_GENERIC = 24;
+constexpr double Z2_GENERIC_SERIES = 49.0;
+
+__device__ inline DW dw_generic(double x, double a) {
+    const double r2 = x * x + a * a;
+    if (a > 0.1 && r2 >= Z2_GENERIC_SERIES && r2 <= 1.79e308) return dw_wing<NWING_GENERIC>(x, a);
+    if (a > 0.1 && r2 < Z2_GENERIC_SERIES) {
+        W2 w = w_alg916(fabs(x), a);
+        if (x < 0.0) w.L = -w.L;
+        return dw_from_w(x, a, w);
+    }
+    return dw_from_w(x, a, w_generic(x, a));              // a < 0 (reflection), NaN, |z|^2 beyond the range
+}
+
+// LC_MODE[0] of a line's record as fill_record sets it from a (finite T): 0: 0 <= a <= 0.1, 1: 0.1 < a < 7, 2: a >= 7 or a < 0,
+// 3: not finite.  For the test hook, which has no record.
+__device__ __forceinline__ int dw_mode(double a) {
+    if (!(fabs(a) <= 1.79e308)) return 3;
+    if (!(a >= 0.0) || !(a < 7.0)) return 2;
+    return a > 0.1 ? 1 : 0;
+}
+
+// The derivatives of w at one pixel of one line: what grad_lines_kernel accumulates and what the test hook vp_voigt_dw shows.
+// `mode`, `nodd`: LC_MODE of the line's record (wave-uniform); mode 0: every lane of the wave must be active (dw_fast).
+__device__ __forceinline__ DW dw_line(double x, double a, double ea2, int mode, int nodd) {
+    return (mode == 0) ? dw_fast(x, a, ea2, nodd) : dw_generic(x, a);
+}
+
+// Fast domain (0 <= a <= 0.1), tier by wavefront like line_tau_wofz: every lane of the wave must be active.  Only the hook
+// vp_voigt_w calls it: its |x| >= 8 series (w_wing) are the hook's own, the gradient kernels take dw_wing there.
 __device__ __forceinline__ W2 w_fast(double x, double a, double ea2, int nodd) {
     const double xa = fabs(x);
     const bool nanx = !(xa <= 1.79e308);

@@ -377,6 +377,15 @@ class Engine(_Handle):
         self._check(self._lib.vp_voigt_w(self._ctx, a.size, _dp(a), x.size, _dp(x), _dp(H), _dp(L)))
         return H, L
 
+    def voigt_dw(self, a, x):
+        """(H, Hx, G) = (Re w, Re w', Re (z w)') at z = x_j + i a_i, grids on the device: test hook on the device function
+        the gradient kernels take their per-pixel derivatives from."""
+        self._guard()
+        a, x = _f64(a).ravel(), _f64(x).ravel()
+        H, Hx, G = (np.empty((a.size, x.size), dtype=np.float64) for _ in range(3))
+        self._check(self._lib.vp_voigt_dw(self._ctx, a.size, _dp(a), x.size, _dp(x), _dp(H), _dp(Hx), _dp(G)))
+        return H, Hx, G
+
     # -- analytic gradient (vp_lnprob_grad_batch) --------------------------------------------------
     def lnprob_grad(self, theta):
         """(W, D) host array -> (lnprob (W,), grad (W, D)): lnprob and its analytic gradient, reverse mode on the GPU.

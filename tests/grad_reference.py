@@ -37,29 +37,41 @@ def lsf_transpose(q, taps, lsf_mode):
     return u
 
 
+HXG_SERIES_Z = 7.0          # |z| from which _hx_g sums the asymptotic series
+HXG_SERIES_TERMS = 24
+
+
 def _hx_g(x, a, H, L):
     """H_x and G = H + a H_a + x H_x (so that d tau / d b = -(A / b) G: a and x are both proportional to 1/b).
-    From H and L both are small differences of large terms in the wings (H_x ~ a/x^3 from two terms ~ a/x, G ~ a/x^4 from
-    terms ~ a/x^2: a Lorentzian wing does not depend on b) and lose x^2 ulp -- more than the tolerance of the GPU tests for a
-    line that lies outside the spectrum.  For |x| >= 30 the asymptotic series of w' and (z w)' are summed instead
-    (c_m = (2m-1)!!/2^m, s = 1/z^2; eight terms: below 1e-20 relative there):
-        w' = -(i/sqrt(pi)) s sum (2m+1) c_m s^m,      (z w)' = -(i/sqrt(pi)) (1/z) sum 2m c_m s^m."""
+    From H and L both are small differences of large terms once |z| is large (H_x ~ a/x^3 from two terms ~ a/x, G ~ a/x^4 from
+    terms ~ a/x^2: a Lorentzian wing does not depend on b; for large a the same at every x) and lose |z|^2 and |z|^4 ulp -- more
+    than the tolerance of the GPU tests for a line that lies outside the spectrum, or one with a > 0.1.  For |z| >= 7 the
+    asymptotic series of w' and (z w)' are summed instead (c_m = (2m-1)!!/2^m, s = 1/z^2):
+        w' = -(i/sqrt(pi)) s sum (2m+1) c_m s^m,      (z w)' = -(i/sqrt(pi)) (1/z) sum 2m c_m s^m,
+    24 terms (the terms shrink up to m = |z|^2 = 49; the first one left out is 1e-13 of the sum at |z| = 7), in real arithmetic
+    on (Re, Im) pairs: complex division would round Im s ~ a/x^3 against |s| ~ 1/x^2 and lose x/a ulp for a narrow line.
+    For a <= 0.1 the series start at |z| = 8: the Gaussian exp(-x^2) (1 - 2 x^2), which no term of the series holds, is 5e-20 at
+    |x| = 7 beside G = 8e-4 a there, 6e-11 of it for a = 1e-6; at |x| = 8 it is 3e-17 of it.
+    Against the 40-digit grid (tests/test_grad_tiers.py) this is within 2e-13 of the scales of tests/golden/make_wgrid.py from
+    |z| = 7 on; below, scipy's H decides (worst: 4.2e-11 of G's scale at a = 0.1, |x| = 6.1, where wofz is 5e-14 |H| off)."""
+    x, a, H, L = np.broadcast_arrays(*(np.asarray(v, dtype=np.float64) for v in (x, a, H, L)))
     Hx = -2 * (x * H - a * L)
     Ha = 2 * (x * L + a * H) - 2 / np.sqrt(np.pi)
     G = H + a * Ha + x * Hx
-    far = np.abs(x) >= 30.0
+    far = (x * x + a * a >= 64.0) | ((x * x + a * a >= HXG_SERIES_Z ** 2) & (a > 0.1))
     if np.any(far):
-        z = np.where(far, x + 1j * a, 1.0)
-        s = 1.0 / (z * z)
-        c = np.cumprod(np.concatenate([[1.0], 0.5 * (2 * np.arange(1, 8) - 1)]))
-        P1 = np.zeros_like(s)
-        P2 = np.zeros_like(s)
-        for m in range(7, -1, -1):
-            P1 = P1 * s + (2 * m + 1) * c[m]
-            P2 = P2 * s + (2 * m) * c[m]
-        k = -1j / np.sqrt(np.pi)
-        Hx = np.where(far, (k * s * P1).real, Hx)
-        G = np.where(far, (k * P2 / z).real, G)
+        xf, af = np.where(far, x, HXG_SERIES_Z), np.where(far, a, 0.0)
+        inv = 1.0 / (xf * xf + af * af)
+        zr, zi = xf * inv, -af * inv                              # 1/z
+        sr, si = zr * zr - zi * zi, 2.0 * zr * zi                 # 1/z^2
+        c = np.cumprod(np.concatenate([[1.0], 0.5 * (2 * np.arange(1, HXG_SERIES_TERMS) - 1)]))
+        p1r, p1i, p2r, p2i = (np.zeros_like(sr) for _ in range(4))
+        for m in range(HXG_SERIES_TERMS - 1, -1, -1):
+            p1r, p1i = p1r * sr - p1i * si + (2 * m + 1) * c[m], p1r * si + p1i * sr
+            p2r, p2i = p2r * sr - p2i * si + (2 * m) * c[m], p2r * si + p2i * sr
+        k = 1.0 / np.sqrt(np.pi)                                  # Re (-i k (u + i v)) = k v
+        Hx = np.where(far, k * (sr * p1i + si * p1r), Hx)
+        G = np.where(far, k * (zr * p2i + zi * p2r), G)
     return Hx, G
 
 

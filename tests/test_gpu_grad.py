@@ -45,19 +45,31 @@ def _check_rows(eng, thetas, lb, ub, insts, label):
 
 
 # ---- 1. w(z) -------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("order", ["sorted", "mixed"])
+W_BANDS = [0.0, 8.0, 15.0, 36.0, 140.0, 600.0, 1e4, np.inf]          # w_fast: core, then w_wing<14>, <9>, <6>, <4>, <3>, <2>
+
+
+@pytest.mark.parametrize("order", ["sorted", "mixed", "banded"])
 def test_voigt_w_against_high_precision_grid(order):
+    """`sorted`, `mixed`: one call, 95 x = two waves per a, each with core pixels in it: every |x| >= 8 of the fast domain goes
+    through the per-lane blend with w_wing<NWING>.  `banded`: one call per |x| band of w_fast (one wave per a, idle lanes hold
+    the band's last x), so that the ballots pick the band's own shorter series."""
     import rbvfit_amd
     z = np.load(os.path.join(HERE, "golden", "wgrid", "wgrid.npz"))
     a, x, H, L = z["a"], z["x"], z["H"], z["L"]
-    idx = np.argsort(x) if order == "sorted" else np.random.default_rng(5).permutation(x.size)
+    gH, gL = np.empty_like(H), np.empty_like(L)
     with rbvfit_amd.Engine(0) as eng:
-        gH, gL = eng.voigt_w(a, x[idx])
-    H, L = H[:, idx], L[:, idx]
+        if order == "banded":
+            for lo, hi in zip(W_BANDS[:-1], W_BANDS[1:]):
+                m = np.nonzero((np.abs(x) >= lo) & (np.abs(x) < hi))[0]
+                assert 0 < m.size <= 64
+                gH[:, m], gL[:, m] = eng.voigt_w(a, x[m])
+        else:
+            idx = np.argsort(x) if order == "sorted" else np.random.default_rng(5).permutation(x.size)
+            gH[:, idx], gL[:, idx] = eng.voigt_w(a, x[idx])
     floor = 1e-17 * (a[:, None] == 0)
     eH = np.abs(gH - H) / np.maximum(np.abs(H), 1e-300)
     eL = np.abs(gL - L) / np.maximum(np.maximum(np.abs(L), np.abs(H)), 1e-300)
-    print("worst |dH|/|H| = %.3e, worst |dL|/max(|L|,|H|) = %.3e" % (np.max(np.where(np.abs(gH - H) <= floor, 0, eH)), eL.max()))
+    print("%s: worst |dH|/|H| = %.3e, worst |dL|/max(|L|,|H|) = %.3e" % (order, np.max(np.where(np.abs(gH - H) <= floor, 0, eH)), eL.max()))
     assert np.all(np.abs(gH - H) <= 1e-12 * np.abs(H) + floor)
     assert np.all(np.abs(gL - L) <= 1e-12 * np.maximum(np.abs(L), np.abs(H)))
 

@@ -14,7 +14,7 @@ import grad_reference as gr
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 GOLD = os.path.join(HERE, "golden")
-NEW_SYMBOLS = ["vp_lnprob_grad_batch", "vp_lnprob_grad_batch_device", "vp_voigt_w"]
+NEW_SYMBOLS = ["vp_lnprob_grad_batch", "vp_lnprob_grad_batch_device", "vp_voigt_w", "vp_voigt_dw"]
 FD_FIXTURES = ["c0_mgii", "c0_mgii_nolsf", "c3_mini", "tiny_7px", "dla_lya"]
 
 
