@@ -196,6 +196,30 @@ int vp_lnprob_grad_batch(vp_ctx* ctx, int W, int D, const double* theta, double*
 int vp_lnprob_grad_batch_device(vp_ctx* ctx, int W, int D, const double* d_theta, double* d_lnprob, double* d_grad,
                                 void* hip_stream);
 
+/* The model Jacobian J = d model_flux / d theta of one instrument for a batch: out is row-major (W, D, P) host memory, row k of a
+ * walker = the derivative of its (W, P) vp_model_flux_batch row with respect to theta_k (convolved = 0: of the profile before
+ * the LSF).  Analytic, fp64, from the per-pixel derivatives the gradient kernels use (H, Re w', Re (z w)'); tied parameters
+ * (a doublet's two lines share N, b, v) are folded, lines summed in line order; an index no line of the instrument carries
+ * gets a row of zeros.  Like vp_model_flux_batch it does not consult the prior: every row is evaluated (a NaN in theta gives
+ * NaN rows).  Refusals: as vp_lnprob_grad_batch (VP_VOIGT_FAST, NaN wavelength samples, on any instrument of the context). */
+int vp_model_flux_jacobian(vp_ctx* ctx, int inst, int W, int D, const double* theta, double* out, int convolved);
+
+/* lnprob AND the Fisher matrix F = sum_inst J^T W J (W = diag(inv_sigma2), J after the LSF) for a batch of walker rows: lnprob
+ * is (W), fisher is row-major (W, D, D), host memory; symmetric to the bit.  Its inverse is the covariance of theta at a best
+ * fit, off-diagonal terms included (rbvfit_amd.vfit.covariance_from_fisher) -- what the reference's quick fit approximates by
+ * one-dimensional chi^2 curvatures on a 1 % stencil (quick_fit_interface.py:87-128).  The rules are vp_lnprob_grad_batch's:
+ * lnprob comes from the value path's own launches; a row outside the box, with a NaN in theta or with a non-finite lnlike gets
+ * that lnprob and a (D, D) block of NaN, and no model is evaluated for it; finite rows next to such rows are unaffected.  No
+ * atomics, fixed reduction trees (pixel chunks in order, then instruments in order): a row's bits depend on that row alone,
+ * not on the batch it is in, nor on the call.  Refused with VP_EINVAL and a vp_last_error text, never a fallback: VP_VOIGT_FAST
+ * instruments and NaN wavelength samples.  Not in this version: there is no vp_multi_*, gather or sampler form of these
+ * entries, and the Python consumers refuse host-callable instruments. */
+int vp_fisher_batch(vp_ctx* ctx, int W, int D, const double* theta, double* lnprob, double* fisher);
+
+/* Same, operands already resident on the context's GPU; enqueued on `hip_stream` (NULL = the context's own stream) and NOT
+ * synchronised, like vp_lnprob_grad_batch_device.  Same bits as the host entry. */
+int vp_fisher_batch_device(vp_ctx* ctx, int W, int D, const double* d_theta, double* d_lnprob, double* d_fisher, void* hip_stream);
+
 /* w(x_j + i a_i) = H + i L on the device for a grid (host buffers; H and L are row-major (na, nx)).  Test hook, like
  * vp_voigt_h, for the complex tiers the gradient kernels form their derivatives from: the core series (|x| < 8, 0 <= a <= 0.1) and
  * the evaluation outside the fast domain (a > 0.1, a < 0).  Its series for |x| >= 8, 0 <= a <= 0.1 are this hook's own: the
@@ -367,7 +391,7 @@ const char* vp_last_error(const vp_ctx* ctx);
 
 /* Library version string: "rbvfit_amd " RBVFIT_AMD_VERSION " (gfx950, hip)".  One number for the header, the library and the
  * Python package (rbvfit_amd.__version__); tests/test_cabi_symbols.py checks that they agree. */
-#define RBVFIT_AMD_VERSION "0.5.0"
+#define RBVFIT_AMD_VERSION "0.6.0"
 const char* vp_version(void);
 
 #ifdef __cplusplus

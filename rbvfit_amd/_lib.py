@@ -58,6 +58,9 @@ SIGNATURES = {
     "vp_model_flux_components": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, _dp, _dp]),
     "vp_lnprob_grad_batch": (C.c_int, [_ctx, C.c_int, C.c_int, _dp, _dp, _dp]),
     "vp_lnprob_grad_batch_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vp_model_flux_jacobian": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int]),
+    "vp_fisher_batch": (C.c_int, [_ctx, C.c_int, C.c_int, _dp, _dp, _dp]),
+    "vp_fisher_batch_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vp_voigt_w": (C.c_int, [_ctx, C.c_int, _dp, C.c_int, _dp, _dp, _dp]),
     "vp_voigt_dw": (C.c_int, [_ctx, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "vp_voigt_h": (C.c_int, [_ctx, C.c_int, _dp, C.c_int, _dp, _dp]),

@@ -12,6 +12,7 @@
 //   capi_multi.inc        vp_multi_* (several device contexts, one process)
 //   capi_misc.inc         test hooks, timing, introspection
 //   capi_grad.inc         vp_lnprob_grad_batch* (analytic gradient, grad_kernels.h), vp_voigt_w, vp_voigt_dw
+//   capi_fisher.inc       vp_model_flux_jacobian, vp_fisher_batch* (Jacobian and Fisher matrix, fisher_kernels.h)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,6 +34,7 @@
 #include "sampler_kernels.h"
 #include "slice_kernels.h"
 #include "grad_kernels.h"
+#include "fisher_kernels.h"
 
 #include "capi_context.inc"
 #include "capi_launch.inc"
@@ -47,5 +49,6 @@ extern "C" {
 #include "capi_multi.inc"
 #include "capi_misc.inc"
 #include "capi_grad.inc"
+#include "capi_fisher.inc"
 
 }  // extern "C"

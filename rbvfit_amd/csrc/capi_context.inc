@@ -140,6 +140,8 @@ struct Instrument {
                                        // far-field masks are compared with, vp_last_farfield_info)
     bool same_lines_as_prev = false;   // this instrument's records ARE the previous instrument's (same line tables):
                                        // its record-preparation launch is skipped (C3: two instruments, one physics)
+    int* fisher_off = nullptr;         // (D + 1) fisher_rows_kernel: where the terms of theta index k start in fisher_terms
+    int2* fisher_terms = nullptr;      // (3 L) (line, kind) by theta index, then line, then kind; made at the first Fisher / Jacobian call
 };
 
 }  // namespace
@@ -252,6 +254,14 @@ struct vp_ctx {
         double* io = nullptr;     // host entry: theta | grad | lnprob
         size_t n_fl = 0, n_q = 0, n_rec = 0, n_part = 0, n_io = 0;
     } grad;
+    // ... and what the Jacobian / Fisher path adds to it (vp_model_flux_jacobian, vp_fisher_batch*, capi_fisher.inc)
+    struct Fisher {
+        double* g = nullptr;      // (rows, D, P) derivative rows before the LSF
+        double* J = nullptr;      // (rows, D, P) d model_flux / d theta
+        double* part = nullptr;   // (rows, chunks, D, D) partial Fisher blocks (upper triangles)
+        double* io = nullptr;     // host entries: theta | lnprob | fisher
+        size_t n_g = 0, n_J = 0, n_part = 0, n_io = 0;
+    } fisher;
     // model_flux / voigt_h scratch
     double* d_scratch = nullptr;
     size_t scratch_bytes = 0;

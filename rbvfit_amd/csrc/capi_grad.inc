@@ -3,15 +3,15 @@
 namespace {
 
 // What the gradient path does not take (refused with VP_EINVAL, never a fallback).
-int grad_refusals(vp_ctx* c) {
+int grad_refusals(vp_ctx* c, const char* entry = "vp_lnprob_grad_batch", const char* what = "analytic gradient") {
     for (size_t k = 0; k < c->inst.size(); ++k) {
         const Instrument& in = c->inst[k];
         if (in.dev.method != VP_VOIGT_WOFZ)
-            return fail(c, VP_EINVAL, "vp_lnprob_grad_batch: instrument " + std::to_string(k) +
-                        " uses voigt_method 'fast' (piecewise formula): no analytic gradient");
+            return fail(c, VP_EINVAL, std::string(entry) + ": instrument " + std::to_string(k) +
+                        " uses voigt_method 'fast' (piecewise formula): no " + what);
         if (in.nanfix)
-            return fail(c, VP_EINVAL, "vp_lnprob_grad_batch: instrument " + std::to_string(k) +
-                        " has NaN wavelength samples: no analytic gradient");
+            return fail(c, VP_EINVAL, std::string(entry) + ": instrument " + std::to_string(k) +
+                        " has NaN wavelength samples: no " + what);
     }
     return VP_OK;
 }

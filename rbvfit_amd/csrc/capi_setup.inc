@@ -101,7 +101,8 @@ int vp_ctx_destroy(vp_ctx* c) {
     for (auto& in : c->inst) for (void* p : in.allocs) hipFree(p);
     for (void* p : {(void*)c->d_lb, (void*)c->d_ub, (void*)c->d_theta, (void*)c->d_out, (void*)c->d_lc, (void*)c->d_partial,
                     (void*)c->d_flags, (void*)c->d_ticket, (void*)c->d_genflag, (void*)c->d_tile_off, (void*)c->d_sum_logw, (void*)c->d_scratch,
-                    (void*)c->d_ff, (void*)c->grad.fl, (void*)c->grad.q, (void*)c->grad.rec, (void*)c->grad.part, (void*)c->grad.io})
+                    (void*)c->d_ff, (void*)c->grad.fl, (void*)c->grad.q, (void*)c->grad.rec, (void*)c->grad.part, (void*)c->grad.io,
+                    (void*)c->fisher.g, (void*)c->fisher.J, (void*)c->fisher.part, (void*)c->fisher.io})
         if (p) hipFree(p);
     if (c->h_pinned) hipHostFree(c->h_pinned);
     if (c->h_done) hipHostFree(c->h_done);

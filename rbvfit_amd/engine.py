@@ -407,6 +407,38 @@ class Engine(_Handle):
         self._check(self._lib.vp_lnprob_grad_batch_device(self._ctx, int(W), self.ndim, C.c_void_p(d_theta_ptr),
                                                           C.c_void_p(d_lnprob_ptr), C.c_void_p(d_grad_ptr), C.c_void_p(stream_ptr)))
 
+    # -- model Jacobian and Fisher matrix (vp_model_flux_jacobian, vp_fisher_batch) ---------------------
+    def model_flux_jacobian(self, inst: int, theta, convolved: bool = True) -> np.ndarray:
+        """(W, D) host array -> (W, D, P): d model_flux / d theta_k of instrument ``inst``, analytic, on the GPU (``convolved=False``:
+        of the profile before the LSF).  Like ``model_flux`` it does not consult the prior."""
+        self._guard()
+        th = self._theta2d(theta)
+        W = th.shape[0]
+        out = np.empty((W, self.ndim, self.n_pixels[inst]), dtype=np.float64)
+        self._check(self._lib.vp_model_flux_jacobian(self._ctx, int(inst), W, th.shape[1], _dp(th) if W else None,
+                                                     _dp(out) if W else None, 1 if convolved else 0))
+        return out
+
+    def fisher(self, theta):
+        """(W, D) host array -> (lnprob (W,), F (W, D, D)): lnprob and the Fisher matrix sum_inst J^T W J of every row, symmetric
+        to the bit.  Rows whose lnprob is not finite get a NaN block.  Raises ``RbvfitAmdError`` for instruments with
+        ``voigt_method='fast'`` or NaN wavelength samples."""
+        self._guard()
+        th = self._theta2d(theta)
+        W = th.shape[0]
+        lnp = np.empty(W, dtype=np.float64)
+        F = np.empty((W, self.ndim, self.ndim), dtype=np.float64)
+        self._check(self._lib.vp_fisher_batch(self._ctx, W, th.shape[1], _dp(th) if W else None, _dp(lnp) if W else None,
+                                              _dp(F) if W else None))
+        return lnp, F
+
+    def fisher_device(self, d_theta_ptr: int, d_lnprob_ptr: int, d_fisher_ptr: int, W: int, stream_ptr: int = 0):
+        """Device-resident operands (raw pointers: theta (W, D), lnprob (W), fisher (W, D, D)); asynchronous on ``stream_ptr``
+        like ``lnprob_grad_device``."""
+        self._guard()
+        self._check(self._lib.vp_fisher_batch_device(self._ctx, int(W), self.ndim, C.c_void_p(d_theta_ptr),
+                                                     C.c_void_p(d_lnprob_ptr), C.c_void_p(d_fisher_ptr), C.c_void_p(stream_ptr)))
+
     # -- device-resident ensemble sampler (vp_stretch_run) ---------------------------------------
     def stretch_run(self, pos, nsteps: int, lnprob=None, a: float = 2.0, seed: int = 0, step0: int = 0,
                     store_chain: bool = True, naccepted=None):

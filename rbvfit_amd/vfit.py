@@ -33,6 +33,35 @@ def set_bounds(nguess, bguess, vguess, **kwargs):
     return [lb, ub], lb, ub
 
 
+def covariance_from_fisher(F):
+    """(D, D) Fisher matrix -> (D, D) covariance, its inverse -- or ``ValueError`` when the data do not constrain every
+    parameter.  Pure NumPy.  F is scaled to the correlation form C = F / sqrt(diag x diag) (logN, b and v differ by orders of
+    magnitude in F), eigendecomposed, and inverted only if every F_kk > 0 and lambda_min > D eps lambda_max; the error names
+    the theta indices that dominate the null direction (singular Fisher matrices are normal here: lines outside the
+    spectrum, saturated lines, one-pixel spectra)."""
+    F = np.asarray(F, dtype=np.float64)
+    if F.ndim != 2 or F.shape[0] != F.shape[1]:
+        raise ValueError(f"covariance_from_fisher: expected a square matrix, got shape {F.shape}")
+    D = F.shape[0]
+    if not np.all(np.isfinite(F)):
+        raise ValueError("covariance_from_fisher: the Fisher matrix has non-finite entries")
+    diag = np.diag(F)
+    if not np.all(diag > 0):
+        bad = np.nonzero(~(diag > 0))[0].tolist()
+        raise ValueError(f"covariance_from_fisher: parameters {bad} are not constrained by the data (F_kk <= 0)")
+    s = np.sqrt(diag)
+    C = F / np.outer(s, s)
+    C = 0.5 * (C + C.T)
+    lam, V = np.linalg.eigh(C)
+    if not lam[0] > D * np.finfo(np.float64).eps * lam[-1]:
+        null = np.abs(V[:, 0])
+        bad = np.nonzero(null >= 0.5 * null.max())[0].tolist()
+        raise ValueError(f"covariance_from_fisher: parameters {bad} are not constrained by the data "
+                         f"(scaled Fisher matrix: lambda_min / lambda_max = {lam[0] / lam[-1]:.3e})")
+    cov = (V / lam[None, :]) @ V.T / np.outer(s, s)
+    return 0.5 * (cov + cov.T)
+
+
 def _tables_of(model) -> CompiledModelData:
     if isinstance(model, CompiledModelData):
         return model
@@ -240,6 +269,27 @@ class vfit:
         lp, g = self.engine.lnprob_grad(np.atleast_2d(th))
         return (float(lp[0]), g[0]) if th.ndim == 1 else (lp, g)
 
+    def fisher(self, theta):
+        """lnprob and the Fisher matrix F = sum_inst J^T W J (``Engine.fisher``: J = d model_flux / d theta after the LSF,
+        W = inv_sigma2).  (D,) -> (float, (D, D)); (W, D) -> ((W,), (W, D, D)).  Rows whose lnprob is not finite get a NaN
+        block.  Host-callable instruments have no analytic Jacobian: refused."""
+        if self._host_instruments:
+            raise NotImplementedError("fisher: host-callable instruments have no analytic Jacobian (use the curvature errors)")
+        th = np.asarray(theta, dtype=np.float64)
+        lp, F = self.engine.fisher(np.atleast_2d(th))
+        return (float(lp[0]), F[0]) if th.ndim == 1 else (lp, F)
+
+    def covariance(self, theta):
+        """(D,) -> (D, D): the covariance of theta at ``theta``, the inverse of the Fisher matrix (``covariance_from_fisher``;
+        ``ValueError`` when the data do not constrain every parameter, or when lnprob is not finite at ``theta``)."""
+        th = np.asarray(theta, dtype=np.float64)
+        if th.ndim != 1:
+            raise ValueError("covariance: theta must be one (D,) row")
+        lp, F = self.fisher(th)
+        if not np.isfinite(lp):
+            raise ValueError(f"covariance: lnprob is {lp} at theta (outside the bounds, or a non-finite likelihood)")
+        return covariance_from_fisher(F)
+
     # L-BFGS-B with the analytic gradient: scipy's default ftol (2.2e-9 relative, i.e. ~2e-5 on an lnprob of 1e4) is sized for
     # finite-difference slopes; an exact gradient lets the search go on to where the slope itself vanishes
     _ANALYTIC_OPTIONS = {"ftol": 1e-12, "gtol": 1e-8}
@@ -277,11 +327,17 @@ class vfit:
         out = -2.0 * np.atleast_1d(self.lnlike(np.atleast_2d(th))) + const
         return float(out[0]) if th.ndim == 1 else out
 
-    def estimate_parameter_errors(self, theta_best, theta_initial=None, delta_frac: float = 0.01):
+    def estimate_parameter_errors(self, theta_best, theta_initial=None, delta_frac: float = 0.01, method: str = "curvature"):
         """Mirror of ``_estimate_parameter_errors`` (quick_fit_interface.py:87-128): curvature of chi2
         along each axis from central differences, sigma = 1/sqrt(d2chi2) -- the 2D+1 evaluations are
-        ONE batch.  Non-positive curvature falls back to |theta_best - theta_initial|."""
+        ONE batch.  Non-positive curvature falls back to |theta_best - theta_initial|.
+        ``method='fisher'``: sqrt(diag(covariance(theta_best))) instead -- the marginal errors, degeneracies included, at the
+        accuracy of the analytic gradient; ``ValueError`` when the Fisher matrix is singular."""
+        if method not in ("curvature", "fisher"):
+            raise ValueError(f"method must be 'curvature' or 'fisher'; got {method!r}")
         tb = np.asarray(theta_best, dtype=np.float64)
+        if method == "fisher":
+            return np.sqrt(np.diag(self.covariance(tb)))
         ti = np.asarray(self.theta if theta_initial is None else theta_initial, dtype=np.float64)
         D = tb.size
         delta = np.maximum(np.maximum(np.abs(tb) * delta_frac, np.abs(ti) * delta_frac), 1e-6)
@@ -292,21 +348,27 @@ class vfit:
             err = np.where(d2 > 0, np.sqrt(1.0 / d2), np.abs(tb - ti))
         return err
 
-    def fit_quick(self, verbose: bool = False, eps: float = 1e-8, grad: str = "fd"):
+    def fit_quick(self, verbose: bool = False, eps: float = 1e-8, grad: str = "fd", errors: str = "curvature"):
         """Mirror of ``vfit.fit_quick`` (vfit_mcmc.py:362-406 -> quick_fit_interface.py:10-84):
         L-BFGS-B on chi2 inside the bounds (``maxfun=5000``), then curvature errors.  The
         finite-difference gradient scipy would build serially is one (D+1)-row GPU batch per
         iteration (``grad='fd'``, the default); ``grad='analytic'`` takes chi2 and its gradient from
         ``lnprob_grad`` instead (chi2 = -2 lnlike + sum log w, so its gradient is -2 x the lnlike gradient;
         inside the bounds the box prior adds nothing).  Returns (theta_best, theta_best_error) and
-        stores them on the object."""
+        stores them on the object.  ``errors='fisher'`` takes the errors from the inverse Fisher matrix at the best fit and
+        stores that covariance as ``theta_best_cov``; where the Fisher matrix is singular it warns, falls back to the
+        curvature errors and stores ``theta_best_cov = None`` (the reference's own manner: fall back, do not fail a fit)."""
         import warnings
         import scipy.optimize as op
         self.mcmc_flag = False
         lb, ub = self.lb, self.ub
         analytic = self._grad_mode(grad)
+        if errors not in ("curvature", "fisher"):
+            raise ValueError(f"errors must be 'curvature' or 'fisher'; got {errors!r}")
         if analytic and self._host_instruments:
             raise NotImplementedError("fit_quick: host-callable instruments have no analytic gradient (use grad='fd')")
+        if errors == "fisher" and self._host_instruments:
+            raise NotImplementedError("fit_quick: host-callable instruments have no analytic Jacobian (use errors='curvature')")
         const = sum(float(np.sum(np.asarray(e["log_inv_sigma2"], dtype=np.float64))) for e in self.instrument_data.values())
 
         def objective_analytic(th):
@@ -328,14 +390,25 @@ class vfit:
             res = op.minimize(objective, np.asarray(self.theta, dtype=np.float64), jac=True, method="L-BFGS-B",
                               bounds=list(zip(lb, ub)), options=dict({"maxfun": 5000}, **(self._ANALYTIC_OPTIONS if analytic else {})))
             theta_best = res.x
-            theta_err = self.estimate_parameter_errors(theta_best, self.theta)
+            theta_cov = None
+            if errors == "fisher":
+                try:
+                    theta_cov = self.covariance(theta_best)
+                    theta_err = np.sqrt(np.diag(theta_cov))
+                except ValueError as e:
+                    warnings.warn(f"Fisher errors not available ({e}); using the curvature errors")
+            if theta_cov is None:
+                theta_err = self.estimate_parameter_errors(theta_best, self.theta)
             if not res.success:
                 warnings.warn(f"Optimization may not have converged: {res.message}")
         except Exception as e:                                # quick_fit_interface.py:79-82
             warnings.warn(f"Minimize fitting failed: {e}")
             theta_best = np.array(self.theta, dtype=np.float64)
             theta_err = np.zeros_like(theta_best)
+            theta_cov = None
         self.theta_best, self.theta_best_error = theta_best, theta_err
+        if errors == "fisher":
+            self.theta_best_cov = theta_cov
         return theta_best, theta_err
 
     # -- walker loop (host) ----------------------------------------------------------------------
