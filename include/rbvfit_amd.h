@@ -372,6 +372,11 @@ int vp_last_launch_kind(const vp_ctx* ctx);
  * vfit_mcmc.py:127-135).  A row's value is then that of the one-pass tile launches (option "geom" = 1) bit for bit, whatever the
  * number of groups; it can differ in the last bit from the ordinary form's (two-pass tile sums), which is why it is opt-in. */
 int vp_last_walker_split(const vp_ctx* ctx);
+/* walker_kernel's deals of an instrument's tiles to the waves of a walker's workgroup (option "walker_perm"): deals[0] for batches of
+ * at most one workgroup per compute unit, deals[1] for batches that put several on one; nibble k = the tile of wave k.  *ntiles = tiles (= waves) per walker, *ntask = the leading waves that also form the records (they hold the cheapest
+ * tiles of both deals), cost[0 .. max_tiles) = the estimated cost of each tile the deals were made from (pixels within 300 km/s of a
+ * line centre; all zero where no deal was made: more than 16 tiles).  Any pointer may be NULL. */
+int vp_walker_deals(const vp_ctx* ctx, int inst, uint64_t deals[2], int64_t* cost, int max_tiles, int* ntiles, int* ntask);
 /* What the far-field expansions of the last lnprob batch covered (first instrument that took any; test / diagnosis hook, it
  * synchronises and copies the masks back): *variant = 0 none, 1 farfield_kernel<6,false> (lines outside clusters and whole
  * clusters, |x| >= 30), 2 farfield_kernel<9,true> (narrow-pixel instruments: also the MEMBERS of clusters too near for their

@@ -57,8 +57,9 @@ struct Tuning {
                                 // size (the lnprob rule), 0 never, 1 whenever the instrument has the tables
     int walker_prio = -1;       // walker_kernel: raised issue priority for the waves with line cores: -1 where workgroups share a CU, 0 never, 1 always
     long walker_perm_hex = 0;   // (experiments) an explicit WalkerArgs::wperm
-    int walker_perm = -1;       // walker_kernel deals its tiles to the waves by estimated cost (WalkerArgs::wperm): -1 for batches of at most
-                                // one workgroup per CU, 0 never (wave k takes tile k), 1 always
+    int walker_perm = -1;       // walker_kernel deals its tiles to the waves by estimated cost (WalkerArgs::wperm): -1 by batch size (at most
+                                // one workgroup per CU: the cost deal; more: the grid-order deal with the line-core tiles behind the entry
+                                // waves, walker_deal_for), 0 never (wave k takes tile k), 1 always the cost deal, 2 always the grid-order deal
     int stretch_overlap = -1;   // vp_stretch_run, half-steps as one launch each: -1 consecutive half-steps on two streams, ordered walker by
                                 // walker through version words (StretchArgs::ovl), where two half-ensembles fit the CUs at once; 0 never
                                 // (every half-step behind the one before, one stream); 1 whenever the half-steps are one launch each
@@ -118,6 +119,9 @@ struct Instrument {
     size_t lds_s = 0;            // LDS bytes of one single-wave ONE-pass tile (dev_s where nwaves == 1): walker_kernel's split form; 0: none
     int* split_hint = nullptr;   // (dev_s.ntiles) the split form's "tile met line cores before" hints (InstDev::core_hint of that launch)
     unsigned long long wperm = 0xFEDCBA9876543210ull;   // walker_kernel (this instrument alone): tile of wave k in nibble k (WalkerArgs)
+    unsigned long long wperm_shared = 0xFEDCBA9876543210ull; // ... for batches of more than one workgroup per CU (walker_deal_for)
+    int deal_ntask = 0;          // waves with entry tasks (they hold the cheapest tiles of both deals) and the tiles' estimated cost:
+    std::vector<long> deal_cost; // what the deals were made from (vp_walker_deals)
 
     vp::LinesDev lines{};
     double sum_logw = 0.0;

@@ -280,13 +280,21 @@ void launch_walker_any(vp_ctx* c, int W, const vp::WalkerArgs& a, const vp::Stre
                        grid, block, lds, s, d0, t0, a, st);
 }
 
-// which deal of tiles to waves a walker launch of W workgroups gets (Tuning::walker_perm)
-unsigned long long walker_perm_for(vp_ctx* c, int W) {
+// which deal of tiles to waves a walker launch of W workgroups gets (Tuning::walker_perm).  At most one workgroup per CU: the cost deal
+// (Instrument::wperm).  More -- 257 ... 512 walkers and the second round up to 1024 on C1's 12 tiles --: the grid-order deal with the
+// line-core tiles behind the entry waves (Instrument::wperm_shared; the identity before: C1 at 512 walkers 21.20 -> 20.80 us per pass,
+// profiles/simd_deal_notes.md).  shared_ok: the plain and the sampler form of the one-instrument launch; the pre-armed and the flux
+// form keep the identity there.
+unsigned long long walker_deal_for(vp_ctx* c, int W, bool shared_ok) {
     const unsigned long long ident = 0xFEDCBA9876543210ull;
-    if (c->inst.size() != 1 || c->tune.walker_perm == 0) return ident;
+    const int mode = c->tune.walker_perm;
+    if (c->inst.size() != 1 || mode == 0) return ident;
     if (c->tune.walker_perm_hex != 0) return (unsigned long long)c->tune.walker_perm_hex;     // (experiments: an explicit deal)
-    if (c->tune.walker_perm > 0) return c->inst[0].wperm;
-    return (ctx_num_cus(c) > 0 && W <= ctx_num_cus(c)) ? c->inst[0].wperm : ident;
+    const Instrument& in = c->inst[0];
+    if (mode == 1) return in.wperm;
+    if (mode == 2 && shared_ok) return in.wperm_shared;
+    if (ctx_num_cus(c) > 0 && W <= ctx_num_cus(c)) return in.wperm;
+    return shared_ok ? in.wperm_shared : ident;
 }
 // raised issue priority for the waves with line cores: where workgroups share a CU (WalkerArgs::prio)
 int walker_prio_for(vp_ctx* c, int W) {
@@ -299,14 +307,14 @@ int walker_prio_for(vp_ctx* c, int W) {
 // row0 -- every workgroup of a walker has its own record rows, so a second launch in flight starts behind row0 x split of them;
 // shared_cus: another launch sits on the CUs at the same time (overlapped half-steps)
 vp::WalkerArgs walker_args(vp_ctx* c, int W, const double* theta, double* out, double sum_logw, int split = 0, int row0 = 0,
-                           bool shared_cus = false) {
+                           bool shared_cus = false, bool shared_ok = false) {
     const Instrument& in = c->inst[0];
     const size_t nrec = (size_t)(in.dev.L + in.dev.NCm) * vp::LC_STRIDE;
     const int per = std::max(1, split);
     vp::WalkerArgs a{theta, c->d_lb, c->d_ub, c->d_lc + (size_t)row0 * per * nrec, out, sum_logw, c->D,
                      (int)((split > 0 ? in.lds_s : walker_wave_lds(c)) / sizeof(double)),
                      (shared_cus && c->tune.walker_prio < 0) ? 1 : walker_prio_for(c, W * per),     // (overlapped half-steps share the CUs)
-                     split > 0 ? 0xFEDCBA9876543210ull : walker_perm_for(c, W)};
+                     split > 0 ? 0xFEDCBA9876543210ull : walker_deal_for(c, W, shared_ok)};
     if (split > 0) { a.split = split; a.split_row0 = row0; a.split_part = c->d_partial; a.split_ticket = c->d_ticket; }
     return a;
 }
@@ -326,7 +334,7 @@ struct LaunchPlan {
 const vp::InstDev& geom_of(const Instrument& x, int sel) { return sel == 2 ? x.dev_w : sel ? x.dev_s : x.dev; }
 
 void launch_walker(vp_ctx* c, const LaunchPlan& p, int W, const double* d_theta, double* d_out, hipStream_t s, bool armed = false) {
-    vp::WalkerArgs a = walker_args(c, W, d_theta, d_out, c->inst[0].sum_logw, p.split);
+    vp::WalkerArgs a = walker_args(c, W, d_theta, d_out, c->inst[0].sum_logw, p.split, 0, false, !armed);
     if (armed) {
         a.arm_slots = c->arm.slots;
         a.arm_slot_doubles = c->arm.slot_doubles;
@@ -350,7 +358,7 @@ void launch_walker(vp_ctx* c, const LaunchPlan& p, int W, const double* d_theta,
 // (lc_row0: first row of the record workspace this launch may use -- two half-steps in flight at once, vp_stretch_run's
 //  overlapped form, must not share rows)
 void launch_walker_stretch(vp_ctx* c, int nS, const vp::StretchArgs& st, hipStream_t s, int lc_row0 = 0, int split = 0) {
-    launch_walker_any<true>(c, nS, walker_args(c, nS, nullptr, nullptr, c->inst[0].sum_logw, split, lc_row0, st.ovl != 0), st, s);
+    launch_walker_any<true>(c, nS, walker_args(c, nS, nullptr, nullptr, c->inst[0].sum_logw, split, lc_row0, st.ovl != 0, true), st, s);
 }
 // whole half-step in one launch (proposal, lnprob, accept inside each walker's workgroup) where the walker kernel
 // applies to a half-ensemble batch and the instrument has no cluster records

@@ -106,6 +106,17 @@ int vp_last_farfield_info(vp_ctx* c, int* variant, int64_t* covered, int64_t* co
     return VP_OK;
 }
 
+int vp_walker_deals(const vp_ctx* c, int inst, uint64_t deals[2], int64_t* cost, int max_tiles, int* ntiles, int* ntask) {
+    if (!c) return VP_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (inst < 0 || inst >= (int)c->inst.size()) return VP_EINVAL;
+    const Instrument& in = c->inst[inst];
+    if (deals) { deals[0] = in.wperm; deals[1] = in.wperm_shared; }
+    if (ntiles) *ntiles = in.dev_w.ntiles;
+    if (ntask) *ntask = in.deal_ntask;
+    for (int t = 0; cost && t < max_tiles; ++t) cost[t] = t < (int)in.deal_cost.size() ? in.deal_cost[t] : 0;
+    return VP_OK;
+}
 int vp_last_launch_kind(const vp_ctx* c) {
     if (!c) return -1;
     std::lock_guard<std::mutex> g(c->mu);

@@ -446,6 +446,28 @@ int vp_add_instrument(vp_ctx* c, int P, const double* wave, const double* flux, 
                     perm = (perm & ~(15ull << (4 * seq[k]))) | ((unsigned long long)tile << (4 * seq[k]));
                 }
                 in.wperm = perm;
+                // ... and the deal for batches that put two workgroups on a CU (Instrument::wperm_shared, walker_deal_for): the tiles stay
+                // in grid order inside three groups -- the cheapest tiles on the waves with entry tasks, then the tiles with line
+                // cores (more than half the largest cost: one per SIMD where there are four), then the rest.  Measured on C1 at 512
+                // walkers, us per pass (profiles/simd_deal_notes.md): grid order 21.20, the deal above 21.67, this one 20.80.
+                {
+                    long cmax = 0;
+                    for (int t = 0; t < nw; ++t) cmax = std::max(cmax, cost[t]);
+                    std::vector<int> asc(nw);
+                    for (int t = 0; t < nw; ++t) asc[t] = t;
+                    std::stable_sort(asc.begin(), asc.end(), [&](int a, int b) { return cost[a] < cost[b]; });     // cheapest first, ties in grid order
+                    std::vector<int> grp(nw, 2);
+                    for (int t = 0; t < nw; ++t) if (cmax > 0 && 2 * cost[t] > cmax) grp[t] = 1;
+                    for (int k = 0; k < ntask; ++k) grp[asc[k]] = 0;
+                    unsigned long long ps = 0xFEDCBA9876543210ull;
+                    int k = 0;
+                    for (int g = 0; g < 3; ++g)
+                        for (int t = 0; t < nw; ++t)
+                            if (grp[t] == g) { ps = (ps & ~(15ull << (4 * k))) | ((unsigned long long)t << (4 * k)); ++k; }
+                    in.wperm_shared = ps;
+                }
+                in.deal_ntask = ntask;
+                in.deal_cost.assign(cost.begin(), cost.end());
             }
             int* d_tabl;
             if ((rc = upload<int>(c, &in, tabl.data(), tabl.size(), &d_tabl))) { for (void* p : in.allocs) hipFree(p); return rc; }

@@ -473,6 +473,17 @@ class Engine(_Handle):
         self._guard()
         return int(self._lib.vp_last_walker_split(self._ctx))
 
+    def walker_deals(self, inst: int = 0) -> dict:
+        """walker_kernel's deals of the instrument's tiles to the waves of a workgroup (``vp_walker_deals``): ``deals`` two lists, tile
+        of wave k for batches of at most one workgroup per compute unit / of more; ``cost`` the tiles' estimated cost;
+        ``ntask`` the leading waves that also form the records."""
+        self._guard()
+        d, cost, nt, ntask = (C.c_uint64 * 2)(), (C.c_int64 * 16)(), C.c_int(0), C.c_int(0)
+        self._check(self._lib.vp_walker_deals(self._ctx, inst, d, cost, 16, C.byref(nt), C.byref(ntask)))
+        n = min(nt.value, 16)
+        return dict(deals=[[(int(x) >> (4 * k)) & 15 for k in range(n)] for x in d], cost=[int(x) for x in cost[:n]],
+                    ntiles=nt.value, ntask=ntask.value)
+
     @property
     def last_farfield_info(self) -> dict:
         """What the far-field expansions of the last lnprob batch covered (``vp_last_farfield_info``): ``variant`` 'none',
