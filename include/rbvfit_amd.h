@@ -220,6 +220,34 @@ int vp_fisher_batch(vp_ctx* ctx, int W, int D, const double* theta, double* lnpr
  * synchronised, like vp_lnprob_grad_batch_device.  Same bits as the host entry. */
 int vp_fisher_batch_device(vp_ctx* ctx, int W, int D, const double* d_theta, double* d_lnprob, double* d_fisher, void* hip_stream);
 
+/* Batched Levenberg-Marquardt fit: every row of theta (W, D; host memory) is a start, and all of them are iterated together on the
+ * GPU, at most nsteps times; theta, F, g and the trial rows stay in device memory, the host reads one word per iteration (rows
+ * still running).  Per row and iteration: F (vp_fisher_batch's launches) and g (vp_lnprob_grad_batch's) where the row has moved;
+ * the damped system on the free set in Marquardt's scaled form, C = F / sqrt(diag x diag), (C + lambda I) y = g / sqrt(diag),
+ * by Cholesky; theta_trial = clip(theta + y / sqrt(diag), lb, ub); its lnprob from the value path; accepted if finite and larger.
+ * Index k is held for a solve (its step is 0) when theta_k sits on a bound and g_k points outward, when F_kk is not positive, or
+ * when F_kk (ub_k - lb_k)^2 < freeze_tol (the data say nothing about it).  lambda follows Nielsen's rule: accepted,
+ * lambda *= max(1/3, 1 - (2 rho - 1)^3) with rho = gain / predicted gain, and nu = 2; rejected (or a pivot that is not
+ * positive), lambda *= nu, nu *= 2.
+ * status (W): 0 still running when nsteps ran out, 1 converged (an accepted gain <= ftol max(1, |lnprob|), or |y|_inf <= xtol: y is
+ * the step in units of each parameter's conditional sigma), 2 the start cannot be evaluated (outside the box, NaN in theta,
+ * non-finite lnprob: its theta row is left as it came, its lnprob, lambda and Fisher block are NaN), 3 stalled (lambda > lambda_max).
+ * Out: theta (the rows where they ended), lnprob (never below the start's), fisher ((W, D, D) at the result; may be NULL), niter
+ * (iterations each row took part in), lambda_out.  opts: lambda0, lambda_max, ftol, xtol, freeze_tol, or NULL for 1e-3, 1e12,
+ * 1e-10, 1e-6, 1e-6.  nsteps = 0 evaluates only: lnprob and F are vp_fisher_batch's bits, status 0 or 2.
+ * No atomics, fixed elimination order: a row's results depend on that row alone.  Refused with VP_EINVAL: D > 96 (the packed
+ * triangle of a row lives in LDS), and what vp_lnprob_grad_batch refuses (VP_VOIGT_FAST, NaN wavelength samples).  No vp_multi_*
+ * form. */
+int vp_lm_run(vp_ctx* ctx, int W, int D, double* theta, double* lnprob, double* fisher, int* status, int* niter, double* lambda_out,
+              int nsteps, const double* opts);
+
+/* Test hook on the solve of one vp_lm_run iteration (lm_step_kernel) for W rows: F (W, D, D), g (W, D), theta (W, D), lambda (W)
+ * -> theta_trial (W, D), pred (W; the predicted gain in lnprob), held (W, D; 1 where the index was held), ok (W; 0 where C + lambda I
+ * is not positive definite: theta_trial is theta then).  Bounds are the context's (vp_set_bounds; no instrument is needed),
+ * freeze_tol is 1e-6.  D <= 96. */
+int vp_lm_solve(vp_ctx* ctx, int W, int D, const double* F, const double* g, const double* theta, const double* lambda,
+                double* theta_trial, double* pred, int* held, int* ok);
+
 /* w(x_j + i a_i) = H + i L on the device for a grid (host buffers; H and L are row-major (na, nx)).  Test hook, like
  * vp_voigt_h, for the complex tiers the gradient kernels form their derivatives from: the core series (|x| < 8, 0 <= a <= 0.1) and
  * the evaluation outside the fast domain (a > 0.1, a < 0).  Its series for |x| >= 8, 0 <= a <= 0.1 are this hook's own: the

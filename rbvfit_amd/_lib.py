@@ -61,6 +61,8 @@ SIGNATURES = {
     "vp_model_flux_jacobian": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int]),
     "vp_fisher_batch": (C.c_int, [_ctx, C.c_int, C.c_int, _dp, _dp, _dp]),
     "vp_fisher_batch_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vp_lm_run": (C.c_int, [_ctx, C.c_int, C.c_int, _dp, _dp, _dp, _ip, _ip, _dp, C.c_int, _dp]),
+    "vp_lm_solve": (C.c_int, [_ctx, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip]),
     "vp_voigt_w": (C.c_int, [_ctx, C.c_int, _dp, C.c_int, _dp, _dp, _dp]),
     "vp_voigt_dw": (C.c_int, [_ctx, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "vp_voigt_h": (C.c_int, [_ctx, C.c_int, _dp, C.c_int, _dp, _dp]),

@@ -13,6 +13,7 @@
 //   capi_misc.inc         test hooks, timing, introspection
 //   capi_grad.inc         vp_lnprob_grad_batch* (analytic gradient, grad_kernels.h), vp_voigt_w, vp_voigt_dw
 //   capi_fisher.inc       vp_model_flux_jacobian, vp_fisher_batch* (Jacobian and Fisher matrix, fisher_kernels.h)
+//   capi_lm.inc           vp_lm_run, vp_lm_solve (batched Levenberg-Marquardt fit, lm_kernels.h)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,6 +36,7 @@
 #include "slice_kernels.h"
 #include "grad_kernels.h"
 #include "fisher_kernels.h"
+#include "lm_kernels.h"
 
 #include "capi_context.inc"
 #include "capi_launch.inc"
@@ -50,5 +52,6 @@ extern "C" {
 #include "capi_misc.inc"
 #include "capi_grad.inc"
 #include "capi_fisher.inc"
+#include "capi_lm.inc"
 
 }  // extern "C"

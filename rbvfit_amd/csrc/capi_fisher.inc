@@ -83,17 +83,24 @@ int fisher_grow_jacobian(vp_ctx* c, int Wc) {
     return VP_OK;
 }
 
-// (called with c->mu held) lnprob by the value path's own launches, then the Jacobian and Fisher launches, all on `s`
-int enqueue_fisher(vp_ctx* c, int W, const double* d_theta, double* d_lnprob, double* d_fisher, hipStream_t s) {
+// the workspace of a W-row Fisher batch
+int fisher_grow(vp_ctx* c, int W) {
     int rc;
     if ((rc = ensure_workspace(c, W))) return rc;
-    const int D = c->D, Wc = fisher_rows_per_pass(c, W, true), T = vp::GRAD_THREADS;
+    const int D = c->D, Wc = fisher_rows_per_pass(c, W, true);
     if ((rc = fisher_grow_jacobian(c, Wc))) return rc;
     size_t n_part = 0;
     for (auto& in : c->inst) n_part = std::max(n_part, (size_t)Wc * fisher_chunks(in.dev.P) * D * D);
     auto& Fw = c->fisher;
-    if ((rc = grad_grow(c, &Fw.part, &Fw.n_part, n_part))) return rc;
-    if ((rc = enqueue_lnprob(c, W, d_theta, d_lnprob, s))) return rc;
+    return grad_grow(c, &Fw.part, &Fw.n_part, n_part);
+}
+
+// (called with c->mu held) the Jacobian and Fisher launches for the rows whose d_lnprob entry is finite (the others get NaN blocks), on `s`
+int enqueue_fisher_rows(vp_ctx* c, int W, const double* d_theta, const double* d_lnprob, double* d_fisher, hipStream_t s) {
+    int rc;
+    if ((rc = fisher_grow(c, W))) return rc;
+    const int D = c->D, Wc = fisher_rows_per_pass(c, W, true), T = vp::GRAD_THREADS;
+    auto& Fw = c->fisher;
     const size_t DD = (size_t)D * D;
     if (DD > 0x7fffffffu) return fail(c, VP_EINVAL, "vp_fisher_batch: D x D does not fit an int");
     hipLaunchKernelGGL(vp::grad_init_kernel, dim3((unsigned)(((size_t)W * DD + T - 1) / T)), dim3(T), 0, s, d_lnprob, W, (int)DD, d_fisher);
@@ -115,6 +122,13 @@ int enqueue_fisher(vp_ctx* c, int W, const double* d_theta, double* d_lnprob, do
     }
     HIP_TRY(c, hipGetLastError());
     return VP_OK;
+}
+
+// (called with c->mu held) lnprob by the value path's own launches, then the Jacobian and Fisher launches, all on `s`
+int enqueue_fisher(vp_ctx* c, int W, const double* d_theta, double* d_lnprob, double* d_fisher, hipStream_t s) {
+    int rc;
+    if ((rc = fisher_grow(c, W)) || (rc = enqueue_lnprob(c, W, d_theta, d_lnprob, s))) return rc;
+    return enqueue_fisher_rows(c, W, d_theta, d_lnprob, d_fisher, s);
 }
 
 }  // namespace

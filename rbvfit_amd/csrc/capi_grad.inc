@@ -33,11 +33,11 @@ int grad_rows_per_pass(const vp_ctx* c, int W) {
     return std::max(1, std::min({W, 32768, (1 << 25) / Pmax}));
 }
 
-// (called with c->mu held) lnprob by the value path's own launches, then the adjoint launches, all on `s`
-int enqueue_lnprob_grad(vp_ctx* c, int W, const double* d_theta, double* d_lnprob, double* d_grad, hipStream_t s) {
+// the workspace of a W-row gradient batch
+int grad_grow_batch(vp_ctx* c, int W) {
     int rc;
     if ((rc = ensure_workspace(c, W))) return rc;
-    const int D = c->D, Wc = grad_rows_per_pass(c, W);
+    const int Wc = grad_rows_per_pass(c, W);
     size_t n_px = 0, n_rec = 0, n_part = 0;
     for (auto& in : c->inst) {
         const size_t nchunk = (in.dev.P + vp::GRAD_CHUNK - 1) / vp::GRAD_CHUNK;
@@ -49,8 +49,15 @@ int enqueue_lnprob_grad(vp_ctx* c, int W, const double* d_theta, double* d_lnpro
     if ((rc = grad_grow(c, &G.fl, &G.n_fl, n_px)) || (rc = grad_grow(c, &G.q, &G.n_q, n_px)) ||
         (rc = grad_grow(c, &G.rec, &G.n_rec, n_rec)) || (rc = grad_grow(c, &G.part, &G.n_part, n_part)))
         return rc;
-    if ((rc = enqueue_lnprob(c, W, d_theta, d_lnprob, s))) return rc;
-    const int T = vp::GRAD_THREADS;
+    return VP_OK;
+}
+
+// (called with c->mu held) the adjoint launches for the rows whose d_lnprob entry is finite (the others get NaN rows), on `s`
+int enqueue_grad_rows(vp_ctx* c, int W, const double* d_theta, const double* d_lnprob, double* d_grad, hipStream_t s) {
+    int rc;
+    if ((rc = grad_grow_batch(c, W))) return rc;
+    const int D = c->D, Wc = grad_rows_per_pass(c, W), T = vp::GRAD_THREADS;
+    auto& G = c->grad;
     hipLaunchKernelGGL(vp::grad_init_kernel, dim3((unsigned)(((size_t)W * D + T - 1) / T)), dim3(T), 0, s, d_lnprob, W, D, d_grad);
     for (auto& in : c->inst) {
         const vp::InstDev& I = in.dev;
@@ -77,6 +84,13 @@ int enqueue_lnprob_grad(vp_ctx* c, int W, const double* d_theta, double* d_lnpro
     }
     HIP_TRY(c, hipGetLastError());
     return VP_OK;
+}
+
+// (called with c->mu held) lnprob by the value path's own launches, then the adjoint launches, all on `s`
+int enqueue_lnprob_grad(vp_ctx* c, int W, const double* d_theta, double* d_lnprob, double* d_grad, hipStream_t s) {
+    int rc;
+    if ((rc = grad_grow_batch(c, W)) || (rc = enqueue_lnprob(c, W, d_theta, d_lnprob, s))) return rc;
+    return enqueue_grad_rows(c, W, d_theta, d_lnprob, d_grad, s);
 }
 
 }  // namespace

@@ -47,6 +47,23 @@ def _ensemble_buffers(pos, nsteps, lnprob, store_chain):
     return pos, lp, have, chain, clp
 
 
+class LMResult:
+    """What ``Engine.lm_run`` returns, all rows: ``theta`` (W, D), ``lnprob`` (W,), ``fisher`` (W, D, D), ``status`` (W,), ``niter`` (W,),
+    ``lam`` (W,)."""
+    __slots__ = ("theta", "lnprob", "fisher", "status", "niter", "lam")
+
+    def __init__(self, theta, lnprob, fisher, status, niter, lam):
+        self.theta, self.lnprob, self.fisher, self.status, self.niter, self.lam = theta, lnprob, fisher, status, niter, lam
+
+    def best(self):
+        """Index of the converged row with the highest lnprob; without one, of the highest finite lnprob (-1: no finite row)."""
+        lp = np.where(np.isfinite(self.lnprob), self.lnprob, -np.inf)
+        conv = self.status == 1
+        if np.any(conv):
+            lp = np.where(conv, lp, -np.inf)
+        return int(np.argmax(lp)) if np.any(lp > -np.inf) else -1
+
+
 class _Handle:
     """What ``Engine`` (a ``vp_ctx``) and ``MultiEngine`` (a ``vp_multi``) have in common: the C handle ``_ctx`` with its lifetime,
     fork guard and error check, and the marshalling of the entry points both kinds of handle have (``_C`` names them)."""
@@ -438,6 +455,47 @@ class Engine(_Handle):
         self._guard()
         self._check(self._lib.vp_fisher_batch_device(self._ctx, int(W), self.ndim, C.c_void_p(d_theta_ptr),
                                                      C.c_void_p(d_lnprob_ptr), C.c_void_p(d_fisher_ptr), C.c_void_p(stream_ptr)))
+
+    # -- batched Levenberg-Marquardt fit (vp_lm_run) ----------------------------------------------
+    _LM_OPTS = ("lambda0", "lambda_max", "ftol", "xtol", "freeze_tol")
+    _LM_DEFAULTS = (1e-3, 1e12, 1e-10, 1e-6, 1e-6)
+
+    def lm_run(self, theta0, nsteps: int = 50, **opts) -> "LMResult":
+        """Levenberg-Marquardt fits from every row of ``theta0`` (W, D) at once, on the GPU (``vp_lm_run``): the Fisher matrix is the
+        Gauss-Newton Hessian, the analytic gradient the right-hand side, one damped solve per row and iteration.  Options:
+        ``lambda0`` 1e-3, ``lambda_max`` 1e12, ``ftol`` 1e-10, ``xtol`` 1e-6, ``freeze_tol`` 1e-6.  Returns an ``LMResult``: ``theta``
+        (W, D), ``lnprob`` (W,), ``fisher`` (W, D, D) at the result, ``status`` (W,) (0 out of iterations, 1 converged, 2 start not
+        evaluable -- theta untouched, the rest NaN --, 3 stalled), ``niter`` (W,), ``lam`` (W,).  Raises ``RbvfitAmdError`` for D > 96,
+        ``voigt_method='fast'`` instruments and NaN wavelength samples."""
+        self._guard()
+        unknown = set(opts) - set(self._LM_OPTS)
+        if unknown:
+            raise TypeError(f"lm_run: unknown options {sorted(unknown)}")
+        th = np.array(self._theta2d(theta0), dtype=np.float64, order="C")
+        W, D = th.shape
+        lnp = np.empty(W, dtype=np.float64)
+        F = np.empty((W, D, D), dtype=np.float64)
+        status, niter = np.zeros(W, dtype=np.int32), np.zeros(W, dtype=np.int32)
+        lam = np.empty(W, dtype=np.float64)
+        o = _f64([float(opts.get(k, v)) for k, v in zip(self._LM_OPTS, self._LM_DEFAULTS)])
+        p = lambda a, conv: conv(a) if W else None
+        self._check(self._lib.vp_lm_run(self._ctx, W, D, p(th, _dp), p(lnp, _dp), p(F, _dp), p(status, _ip), p(niter, _ip), p(lam, _dp),
+                                        int(nsteps), _dp(o)))
+        return LMResult(th, lnp, F, status, niter, lam)
+
+    def lm_solve(self, F, g, theta, lam):
+        """Test hook on one damped solve per row (``vp_lm_solve``): F (W, D, D), g (W, D), theta (W, D), lam (W,) ->
+        (theta_trial (W, D), pred (W,), held (W, D) bool, ok (W,) bool).  Bounds are the engine's; no instrument is needed."""
+        self._guard()
+        th = self._theta2d(theta)
+        W, D = th.shape
+        F, g, lam = _f64(F).reshape(W, D, D), _f64(g).reshape(W, D), _f64(lam).reshape(W)
+        trial, pred = np.empty((W, D), dtype=np.float64), np.empty(W, dtype=np.float64)
+        held, ok = np.zeros((W, D), dtype=np.int32), np.zeros(W, dtype=np.int32)
+        p = lambda a, conv: conv(a) if W else None
+        self._check(self._lib.vp_lm_solve(self._ctx, W, D, p(F, _dp), p(g, _dp), p(th, _dp), p(lam, _dp), p(trial, _dp), p(pred, _dp),
+                                          p(held, _ip), p(ok, _ip)))
+        return trial, pred, held.astype(bool), ok.astype(bool)
 
     # -- device-resident ensemble sampler (vp_stretch_run) ---------------------------------------
     def stretch_run(self, pos, nsteps: int, lnprob=None, a: float = 2.0, seed: int = 0, step0: int = 0,

@@ -348,7 +348,45 @@ class vfit:
             err = np.where(d2 > 0, np.sqrt(1.0 / d2), np.abs(tb - ti))
         return err
 
-    def fit_quick(self, verbose: bool = False, eps: float = 1e-8, grad: str = "fd", errors: str = "curvature"):
+    def fit_lm(self, starts=None, n_starts: int = 32, seed: int = 0, nsteps: int = 50, **opts):
+        """Multi-start Levenberg-Marquardt quick fit on the GPU (``Engine.lm_run``): W starts are iterated together, at the launch
+        count of one.  Row 0 is ``self.theta``, the other ``n_starts - 1`` rows are drawn uniformly in the box with
+        ``np.random.default_rng(seed)`` -- or ``starts`` (W, D) is taken as given.  The best fit is the converged row (status 1) with
+        the highest lnprob; if no row converged, the highest finite lnprob, with a warning.  Errors are those of the inverse Fisher
+        matrix at that row (``covariance_from_fisher``); where it is singular this warns, falls back to the curvature errors and
+        stores ``theta_best_cov = None``, as ``fit_quick(errors='fisher')`` does.  Stores ``theta_best``, ``theta_best_error``,
+        ``theta_best_cov`` and ``lm_result`` (every row: the other minima).  ``opts``: ``lambda0``, ``lambda_max``, ``ftol``, ``xtol``,
+        ``freeze_tol``."""
+        import warnings
+        if self._host_instruments:
+            raise NotImplementedError("fit_lm: host-callable instruments have no analytic gradient or Jacobian (use fit_quick)")
+        self.mcmc_flag = False
+        if starts is None:
+            if n_starts < 1:
+                raise ValueError("fit_lm: n_starts must be >= 1")
+            rng = np.random.default_rng(seed)
+            starts = np.vstack([self.theta[None, :], rng.uniform(self.lb, self.ub, size=(int(n_starts) - 1, self.ndim))])
+        starts = np.atleast_2d(np.asarray(starts, dtype=np.float64))
+        if starts.ndim != 2 or starts.shape[1] != self.ndim or len(starts) == 0:
+            raise ValueError(f"fit_lm: starts must have shape (W, {self.ndim})")
+        res = self.engine.lm_run(starts, nsteps=nsteps, **opts)
+        best = res.best()
+        if best < 0:
+            raise ValueError("fit_lm: no start could be evaluated (outside the bounds, or a non-finite likelihood)")
+        if res.status[best] != 1:
+            warnings.warn(f"fit_lm: no start converged in {nsteps} iterations; taking the highest lnprob (status {int(res.status[best])})")
+        theta_best = res.theta[best].copy()
+        try:
+            theta_cov = covariance_from_fisher(res.fisher[best])
+            theta_err = np.sqrt(np.diag(theta_cov))
+        except ValueError as e:
+            warnings.warn(f"Fisher errors not available ({e}); using the curvature errors")
+            theta_cov = None
+            theta_err = self.estimate_parameter_errors(theta_best, self.theta)
+        self.theta_best, self.theta_best_error, self.theta_best_cov, self.lm_result = theta_best, theta_err, theta_cov, res
+        return theta_best, theta_err
+
+    def fit_quick(self, verbose: bool = False, eps: float = 1e-8, grad: str = "fd", errors: str = "curvature", method: str = "lbfgs"):
         """Mirror of ``vfit.fit_quick`` (vfit_mcmc.py:362-406 -> quick_fit_interface.py:10-84):
         L-BFGS-B on chi2 inside the bounds (``maxfun=5000``), then curvature errors.  The
         finite-difference gradient scipy would build serially is one (D+1)-row GPU batch per
@@ -357,9 +395,15 @@ class vfit:
         inside the bounds the box prior adds nothing).  Returns (theta_best, theta_best_error) and
         stores them on the object.  ``errors='fisher'`` takes the errors from the inverse Fisher matrix at the best fit and
         stores that covariance as ``theta_best_cov``; where the Fisher matrix is singular it warns, falls back to the
-        curvature errors and stores ``theta_best_cov = None`` (the reference's own manner: fall back, do not fail a fit)."""
+        curvature errors and stores ``theta_best_cov = None`` (the reference's own manner: fall back, do not fail a fit).
+        ``method='lm'`` is ``fit_lm(n_starts=1)``: Levenberg-Marquardt on the GPU from ``self.theta`` with Fisher errors (``grad``,
+        ``eps`` and ``errors`` do not apply); the default ``'lbfgs'`` is everything above."""
         import warnings
         import scipy.optimize as op
+        if method not in ("lbfgs", "lm"):
+            raise ValueError(f"method must be 'lbfgs' or 'lm'; got {method!r}")
+        if method == "lm":
+            return self.fit_lm(n_starts=1)
         self.mcmc_flag = False
         lb, ub = self.lb, self.ub
         analytic = self._grad_mode(grad)
