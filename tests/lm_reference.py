@@ -11,7 +11,10 @@
 theta then).
 
 ``run(theta0, lb, ub, instruments, ...)``: the whole fit of one row, with Nielsen's rule for lam and the status codes
-0 running / out of iterations, 1 converged, 2 start not evaluable, 3 stalled (lam > lambda_max).
+0 running / out of iterations, 1 converged, 2 start not evaluable, 3 stalled (lam > lambda_max).  The rule of one iteration is
+``accept(lam, nu, lp, lt, pred, ynorm, ok, ftol, xtol, lambda_max) -> (accepted, lam, nu, status)``, a pure function that ``run``
+calls and that tests/test_gpu_lm_replay.py holds every iteration of ``vp_lm_run`` to; ``ynorm_estimate`` is that test's stand-in
+for the |y|_inf the solve hook does not return.
 """
 import numpy as np
 
@@ -73,7 +76,47 @@ def nielsen_accept(lam, rho):
     return lam * max(1.0 / 3.0, 1.0 - (2.0 * rho - 1.0) ** 3)
 
 
-def run(theta0, lb, ub, instruments, nsteps=50, lambda0=1e-3, lambda_max=1e12, ftol=1e-10, xtol=1e-6, freeze_tol=1e-6):
+def accept(lam, nu, lp, lt, pred, ynorm, ok, ftol, xtol, lambda_max):
+    """The accept rule of one iteration of one row, as ``lm_accept_kernel`` states it -> (accepted, lam, nu, status).
+    lp, lt: lnprob at theta and at the trial point; pred, ynorm (|y|_inf; 0 when every index is held), ok: the solve's."""
+    accepted, status = False, 0
+    if ok:
+        if np.isfinite(lt) and lt > lp:
+            gain = lt - lp
+            accepted = True
+            if gain <= ftol * max(1.0, abs(lp)):
+                status = 1
+            lam, nu = nielsen_accept(lam, gain / pred), 2.0
+        if ynorm <= xtol:
+            status = 1
+    if not accepted:
+        lam, nu = lam * nu, 2.0 * nu
+    if status == 0 and lam > lambda_max:
+        status = 3
+    return accepted, lam, nu, status
+
+
+def ynorm_estimate(trial, theta, F, held, lb, ub, xtol):
+    """|y|_inf read off a solve's outputs, for callers that are not given it (vp_lm_solve returns none) -> (estimate, determined).
+    The estimate is max |trial_k - theta_k| sqrt(F_kk) over the free indices the clip did not touch; it is exact (0) when every
+    index is held.  ``determined`` is False where the estimate cannot say on which side of xtol |y|_inf lies: within a factor 2 of
+    xtol, or at most 2 xtol with a clipped index (whose y_k is unknown).  With xtol = 0 every pair is determined: |y|_inf = 0 with a
+    free index needs gh = 0 to the bit, and the estimate is then reported as the smallest positive double at least."""
+    free = ~held
+    if not np.any(free):
+        return 0.0, True
+    clipped = free & ((trial == lb) | (trial == ub))
+    use = free & ~clipped
+    est = float(np.max(np.abs(trial - theta)[use] * np.sqrt(np.diag(F)[use]))) if np.any(use) else 0.0
+    if xtol == 0.0:
+        return max(est, np.finfo(np.float64).tiny), True
+    if 0.5 * xtol <= est <= 2.0 * xtol or (np.any(clipped) and est <= 2.0 * xtol):
+        return est, False
+    return est, True
+
+
+def run(theta0, lb, ub, instruments, nsteps=50, lambda0=1e-3, lambda_max=1e12, ftol=1e-10, xtol=1e-6, freeze_tol=1e-6, trace=None):
+    """``trace``: a list that receives one dict per iteration (the inputs and outputs of ``accept`` and of the solve)."""
     theta = np.array(theta0, dtype=np.float64)
     lb, ub = np.asarray(lb, dtype=np.float64), np.asarray(ub, dtype=np.float64)
     lp, F, g = evaluate(theta, lb, ub, instruments)
@@ -86,26 +129,19 @@ def run(theta0, lb, ub, instruments, nsteps=50, lambda0=1e-3, lambda_max=1e12, f
         niter += 1
         r = step_full(F, g, theta, lb, ub, lam, freeze_tol)
         held = r["held"]
-        accepted = False
-        if r["ok"]:
-            lt = vo.lnprob(r["theta_trial"], lb, ub, instruments)
-            if np.isfinite(lt) and lt > lp:
-                gain = lt - lp
-                accepted = True
-                if gain <= ftol * max(1.0, abs(lp)):
-                    status = 1
-                lam, nu = nielsen_accept(lam, gain / r["pred"]), 2.0
-                theta, lp = r["theta_trial"], lt
-                nacc += 1
-                history.append(lp)
-            if r["y"].size == 0 or np.max(np.abs(r["y"])) <= xtol:
-                status = 1
-        if not accepted:
-            lam, nu = lam * nu, 2.0 * nu
-        if status == 0 and lam > lambda_max:
-            status = 3
-        if accepted and status == 0:
-            _, F, g = evaluate(theta, lb, ub, instruments)
+        lt = vo.lnprob(r["theta_trial"], lb, ub, instruments) if r["ok"] else np.nan
+        ynorm = float(np.max(np.abs(r["y"]))) if r["y"].size else 0.0
+        rec = dict(lam=lam, nu=nu, lp=lp, lt=lt, pred=r["pred"], ynorm=ynorm, ok=r["ok"], theta=theta, trial=r["theta_trial"], held=held, F=F)
+        accepted, lam, nu, status = accept(lam, nu, lp, lt, r["pred"], ynorm, r["ok"], ftol, xtol, lambda_max)
+        if trace is not None:
+            rec.update(accepted=accepted, lam_out=lam, status=status)
+            trace.append(rec)
+        if accepted:
+            theta, lp = r["theta_trial"], lt
+            nacc += 1
+            history.append(lp)
+            if status == 0:
+                _, F, g = evaluate(theta, lb, ub, instruments)
     if nacc and (status != 0 or niter >= nsteps):
         _, F, g = evaluate(theta, lb, ub, instruments)
     return dict(theta=theta, lnprob=lp, status=status, niter=niter, naccept=nacc, lam=lam, history=history, F=F, g=g, held=held)

@@ -44,20 +44,20 @@ def _bounds_engine(lb, ub):
 
 
 # ---- 1. the solve hook against NumPy -------------------------------------------------------------------------------------
-# D: one lane, below / at / above a wave's 32-lane half, a full wave (64), the two-wave form (96); W: one row, a few, more than a wave of rows
-@pytest.mark.parametrize("D", [1, 2, 3, 6, 24, 31, 32, 33, 64, 96])
-@pytest.mark.parametrize("W", [1, 5, 70])
-def test_solve_against_numpy(D, W):
+def _numpy_rows(D, W):
+    """W well-posed systems of D parameters, cond_2(F) from 1 to 1e6, at theta = 0 inside bounds no step reaches."""
     rng = np.random.default_rng(1000 * D + W)
     lb, ub = -np.full(D, 1e9), np.full(D, 1e9)           # no step is clipped: cond <= 1e6 and lambda >= 1e-6 keep |delta| below 1e7
     F = np.array([_spd(rng, D, 10.0 ** rng.uniform(0, 6)) for _ in range(W)])
     g = rng.standard_normal((W, D))
     theta = np.zeros((W, D))                               # theta_trial is the step itself
     lam = np.array([[1e-3, 1.0, 1e-6][w % 3] for w in range(W)])
-    with _bounds_engine(lb, ub) as eng:
-        trial, pred, held, ok = eng.lm_solve(F, g, theta, lam)
-    assert trial.shape == (W, D) and pred.shape == (W,) and held.shape == (W, D) and ok.shape == (W,)
-    assert np.all(ok) and not np.any(held)
+    return lb, ub, F, g, theta, lam
+
+
+def _check_against_numpy(F, g, lam, trial, pred, label):
+    """The scaled step and pred of every row against np.linalg.solve; returns the worst ratio to the bound."""
+    W, D = g.shape
     worst = 0.0
     for w in range(W):
         s = np.sqrt(np.diag(F[w]))
@@ -68,9 +68,22 @@ def test_solve_against_numpy(D, W):
         bound = 16 * D * EPS * np.linalg.cond(A)
         ratio = np.linalg.norm(y - y_ref) / np.linalg.norm(y_ref) / bound
         worst = max(worst, ratio)
-        assert ratio <= 1.0, "D=%d W=%d row %d: |y - y_ref| / |y_ref| = %.3e x the bound" % (D, W, w, ratio)
+        assert ratio <= 1.0, "%s row %d: |y - y_ref| / |y_ref| = %.3e x the bound" % (label, w, ratio)
         p_ref = (g[w] / s) @ y_ref - 0.5 * y_ref @ C @ y_ref
         assert abs(pred[w] - p_ref) <= 4 * bound * abs(p_ref) + 16 * EPS * abs(p_ref)
+    return worst
+
+
+# D: one lane, below / at / above a wave's 32-lane half, a full wave (64), the two-wave form (96); W: one row, a few, more than a wave of rows
+@pytest.mark.parametrize("D", [1, 2, 3, 6, 24, 31, 32, 33, 64, 96])
+@pytest.mark.parametrize("W", [1, 5, 70])
+def test_solve_against_numpy(D, W):
+    lb, ub, F, g, theta, lam = _numpy_rows(D, W)
+    with _bounds_engine(lb, ub) as eng:
+        trial, pred, held, ok = eng.lm_solve(F, g, theta, lam)
+    assert trial.shape == (W, D) and pred.shape == (W,) and held.shape == (W, D) and ok.shape == (W,)
+    assert np.all(ok) and not np.any(held)
+    worst = _check_against_numpy(F, g, lam, trial, pred, "D=%d W=%d" % (D, W))
     print("D=%d W=%d: worst |y - y_ref|_2 / |y_ref|_2 = %.3f of 16 D eps cond" % (D, W, worst))
 
 
@@ -113,6 +126,139 @@ def test_solve_held_sets():
         assert np.linalg.norm((y - y_ref)[~clipped]) <= 16 * 6 * EPS * np.linalg.cond(A) * np.linalg.norm(y_ref) + slack, w
         assert np.all(trial[w] >= lb) and np.all(trial[w] <= ub)
         assert np.array_equal(trial[w][r["free"]][clipped], r["theta_trial"][r["free"]][clipped])
+
+
+def _held_patterns(D):
+    """Rows of D parameters whose held sets come from the four causes of ``_held_cases`` in random places, and the shapes the
+    compaction of the free indices can get wrong: no free index, one, the ends held, (D > 64) both sides of the seam of the two waves."""
+    rng = np.random.default_rng(4000 + D)
+    want = [rng.random(D) < p for p in (0.1, 0.5, 0.9)]                  # random patterns, sparse to dense
+    want.append(np.ones(D, dtype=bool))                                  # n = 0
+    one = np.ones(D, dtype=bool); one[int(rng.integers(D))] = False      # n = 1
+    want.append(one)
+    ends = np.zeros(D, dtype=bool); ends[[0, D - 1]] = True
+    want.append(ends)
+    if D > 64:
+        seam = rng.random(D) < 0.2; seam[[62, 63, 64]] = True
+        want.append(seam)
+        left = np.zeros(D, dtype=bool); left[:64] = True; left[int(rng.integers(64))] = False      # what is free is nearly all in the second wave
+        want.append(left)
+        right = np.zeros(D, dtype=bool); right[64:] = True               # ... all in the first
+        want.append(right)
+    want = np.array(want)
+    W = len(want)
+    lb, ub = -np.full(D, 50.0), np.full(D, 50.0)
+    F = np.array([_spd(rng, D, 1e3) * np.outer(sc, sc) for sc in 10.0 ** rng.uniform(-1, 1, (W, D))])
+    g = rng.standard_normal((W, D))
+    g[g == 0.0] = 1.0
+    theta = rng.uniform(-1, 1, (W, D))
+    for w in range(W):
+        for k in np.nonzero(want[w])[0]:
+            cause = int(rng.integers(4))
+            if cause == 0:
+                theta[w, k], g[w, k] = lb[k], -abs(g[w, k])              # lower bound, outward
+            elif cause == 1:
+                theta[w, k], g[w, k] = ub[k], abs(g[w, k])               # upper bound, outward
+            elif cause == 2:
+                F[w, k, :] = 0.0; F[w, :, k] = 0.0                       # F_kk = 0
+            else:
+                F[w, k, :] *= 1e-9; F[w, :, k] *= 1e-9                   # F_kk (ub - lb)^2 < freeze_tol
+        for k in np.nonzero(~want[w])[0][:2]:                            # on a bound with the gradient pointing inward: free
+            theta[w, k], g[w, k] = lb[k], abs(g[w, k])
+    return lb, ub, F, g, theta, want
+
+
+# D: above a wave's half, a full wave, one lane into the second wave, the largest
+@pytest.mark.parametrize("D", [33, 64, 65, 96])
+def test_solve_held_sets_wide(D):
+    lb, ub, F, g, theta, want = _held_patterns(D)
+    W = len(want)
+    lam = np.full(W, LAM0)
+    with _bounds_engine(lb, ub) as eng:
+        trial, pred, held, ok = eng.lm_solve(F, g, theta, lam)
+    assert np.all(ok)
+    assert np.array_equal(held, want)
+    assert _same_bits(trial[want], theta[want])            # delta_k == 0 exactly
+    assert np.all(trial >= lb) and np.all(trial <= ub)
+    free_counts = (~want).sum(axis=1).tolist()
+    assert 0 in free_counts and 1 in free_counts
+    worst = 0.0
+    for w in range(W):
+        r = lm.step_full(F[w], g[w], theta[w], lb, ub, LAM0)
+        assert np.array_equal(r["held"], want[w]) and r["ok"]
+        if r["free"].size == 0:                             # every index held: no move, nothing predicted
+            assert pred[w] == 0.0 and _same_bits(trial[w], theta[w])
+            continue
+        A = r["C"] + LAM0 * np.eye(r["free"].size)
+        y_ref = np.linalg.solve(A, r["gh"])
+        y = (trial[w] - theta[w])[r["free"]] * r["s"]
+        clipped = (trial[w][r["free"]] == lb[r["free"]]) | (trial[w][r["free"]] == ub[r["free"]])
+        # theta + delta rounds at eps |theta|: in y that is eps |theta| s_k
+        slack = 2 * EPS * np.linalg.norm(np.maximum(np.abs(theta[w]), np.abs(trial[w]))[r["free"]] * r["s"])
+        bound = 16 * D * EPS * np.linalg.cond(A) * np.linalg.norm(y_ref) + slack
+        worst = max(worst, float(np.linalg.norm((y - y_ref)[~clipped]) / bound))
+        assert np.linalg.norm((y - y_ref)[~clipped]) <= bound, w
+        assert np.array_equal(trial[w][r["free"]][clipped], r["theta_trial"][r["free"]][clipped])
+        assert pred[w] > 0.0 and abs(pred[w] - r["pred"]) <= 4 * 16 * D * EPS * np.linalg.cond(A) * r["pred"]
+    print("D=%d: free indices per row %s, worst |y - y_ref|_2 = %.3f of its bound" % (D, free_counts, worst))
+
+
+@pytest.mark.parametrize("D", [6, 64, 96])
+def test_solve_is_exact_under_powers_of_two(D):
+    """theta_k -> 2^-e_k theta_k, i.e. F' = S F S and g' = S g with S = diag(2^e_k): Marquardt's scaling takes S out again
+    without a rounding, so C, gh, y and pred keep their bits and the step is the old one times 2^-e_k.  Bounds of +-1e30: no step
+    (at most 1e7 x 2^20) is clipped and no F'_kk (ub - lb)^2 (at least 1e-6 x 2^-40 x 4e60) falls under freeze_tol."""
+    _, _, F, g, theta, lam = _numpy_rows(D, 5)
+    rng = np.random.default_rng(D)
+    S = 2.0 ** rng.integers(-20, 21, size=(5, D))
+    F2, g2 = F * S[:, :, None] * S[:, None, :], g * S
+    with _bounds_engine(-np.full(D, 1e30), np.full(D, 1e30)) as eng:
+        trial, pred, held, ok = eng.lm_solve(F, g, theta, lam)
+        trial2, pred2, held2, ok2 = eng.lm_solve(F2, g2, theta, lam)
+    assert np.all(ok) and np.all(ok2) and not np.any(held) and not np.any(held2)
+    assert np.all(trial != 0.0) and len(np.unique(S)) > 8
+    assert _same_bits(trial2 * S, trial) and _same_bits(pred2, pred)
+
+
+def test_solve_non_finite_input_fails_its_row_only():
+    lb, ub, F, g, theta, _ = _held_cases()
+    F, g, theta = F[[0, 7, 0, 7, 0, 7]].copy(), g[[0, 7, 0, 7, 0, 7]].copy(), theta[[0, 7, 0, 7, 0, 7]].copy()      # (rows that hold no index)
+    F[0, 1, 4] = F[0, 4, 1] = np.nan
+    F[1, 2, 5] = F[1, 5, 2] = np.inf
+    g[2, 3] = np.nan
+    g[3, 0] = np.inf
+    F[4, 2, 2] = np.nan                                     # on the diagonal: not F_kk > 0, the index is held
+    lam = np.full(6, LAM0)
+    with _bounds_engine(lb, ub) as eng:
+        trial, pred, held, ok = eng.lm_solve(F, g, theta, lam)
+        solo = [eng.lm_solve(F[[w]], g[[w]], theta[[w]], lam[:1]) for w in (4, 5)]
+    assert ok.tolist() == [False, False, False, False, True, True]
+    assert _same_bits(trial[:4], theta[:4]) and np.all(np.isfinite(pred)) and np.all(pred[:4] == 0.0)
+    assert held[4].tolist() == [False, False, True, False, False, False] and not np.any(held[5]) and not np.any(held[:4])
+    assert trial[4, 2] == theta[4, 2] and np.all(trial[4, [0, 1, 3, 4, 5]] != theta[4, [0, 1, 3, 4, 5]]) and np.all(trial[5] != theta[5])
+    assert np.all(np.isfinite(trial)) and pred[4] > 0.0 and pred[5] > 0.0
+    for n, w in enumerate((4, 5)):
+        assert _same_bits(trial[w], solo[n][0][0]) and _same_bits(pred[w], solo[n][1][0]) and solo[n][3][0]
+    keep = [0, 1, 3, 4, 5]                                  # the row with the NaN on the diagonal is the 5 x 5 system without that index
+    r = lm.step_full(F[4][np.ix_(keep, keep)], g[4][keep], theta[4][keep], lb[keep], ub[keep], LAM0)
+    A = r["C"] + LAM0 * np.eye(5)
+    y = (trial[4] - theta[4])[keep] * r["s"]
+    slack = 2 * EPS * np.linalg.norm(np.maximum(np.abs(theta[4]), np.abs(trial[4]))[keep] * r["s"])
+    unclipped = (trial[4][keep] != lb[keep]) & (trial[4][keep] != ub[keep])
+    assert np.linalg.norm((y - r["y"])[unclipped]) <= 16 * 6 * EPS * np.linalg.cond(A) * np.linalg.norm(r["y"]) + slack
+
+
+@pytest.mark.parametrize("D", [6, 64, 96])
+def test_solve_with_large_and_mixed_damping(D):
+    """lambda = 1e12 on every row, then 1e-12 .. 1e12 within one batch: the bound of test_solve_against_numpy."""
+    lb, ub, F, g, theta, _ = _numpy_rows(D, 5)
+    worst = []
+    with _bounds_engine(lb, ub) as eng:
+        for lam in (np.full(5, 1e12), np.array([1e-12, 1e-6, 1.0, 1e6, 1e12])):
+            trial, pred, held, ok = eng.lm_solve(F, g, theta, lam)
+            assert np.all(ok) and not np.any(held)
+            worst.append(_check_against_numpy(F, g, lam, trial, pred, "D=%d lambda %g .. %g" % (D, lam[0], lam[-1])))
+    print("D=%d: worst |y - y_ref|_2 / |y_ref|_2 = %.3f (lambda 1e12), %.3f (1e-12 .. 1e12) of 16 D eps cond" % (D, worst[0], worst[1]))
 
 
 def test_solve_indefinite_matrix_fails_its_row_only():
